@@ -18,9 +18,16 @@ and the host-gather leg (value_e2e: every output copied to pinned host memory).
 under the driver's `python -m torch.distributed.run ... bench.py --gpus N` it joins the ranks it was given.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HIP-event-timed
-K_sinc launches vs the 8 TB/s HBM peak, 8 algorithmic bytes per output sample) and `cpu_baseline`
-(the plain-C oracle port timed on this box's host cores on a bounded sample), and `parity_checked`: windows of the
-TIMED output buffer compared with the oracle outside the timed region.
+K_sinc launches vs the 8 TB/s HBM peak, 8 algorithmic bytes per output sample).  A plain run does only what that line's
+headline needs: set-up, warm-up, the timed steps, the line.  --full adds everything else the benchmark measures or checks,
+after the timed region: `cpu_baseline` (the plain-C oracle port timed on this box's host cores on a bounded sample), the
+secondary workloads (STFT, config 4, a config-5 work item, NT = 50, `archive_value`) and `parity_checked`: windows of the
+TIMED output buffer compared with the oracle.
+
+--dump-outputs DIR writes what the last timed step computed (single-file mode): DIR/output.npy holds the float32 output
+samples at a fixed, seeded set of positions (all of them when the output is small), DIR/output_index.npy those positions
+(float64) and DIR/output_len.npy the output length.  The inputs are synthesised from fixed seeds, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -137,6 +144,24 @@ def parity_windows(out, sig, st, spd, n_in, n_out, nt, n_windows=16, width=2000)
             "p0_note": "the config-3 end-to-end chain (pyrespeeder on flutter_192.flac) is held to a COUNT bound, not to 1e-5 on every "
                        "sample: 0 of 101 435 dense samples beyond 1e-5, 6 of 9 000 samples of the end window up to 1.42e-5 (the fixture's "
                        "own float32 FFT noise summed by the position cumsum; DESIGN section 2) -- stage-wise 1e-5 holds"}
+
+
+def dump_outputs(dirname, out, n_out, max_samples=1 << 22, seed=0x5EED):
+    """--dump-outputs: the output a caller of the timed path receives (out[:n_out], float32) after the last timed step.  Up to
+    max_samples it is written whole; beyond that at the sorted, distinct positions of max_samples seeded draws over [0, n_out)
+    (the same positions for the same n_out), 4 + 8 B per position: 48 MiB at most."""
+    import numpy as np
+    import torch
+    if n_out <= max_samples:
+        idx = np.arange(n_out, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(seed).integers(0, n_out, size=max_samples, dtype=np.int64))
+    torch.cuda.synchronize()
+    vals = out[:n_out][torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "output.npy"), vals.astype(np.float32, copy=False))
+    np.save(os.path.join(dirname, "output_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "output_len.npy"), np.array([n_out], dtype=np.float64))
 
 
 def stft_secondary(sig, dev, n_fft=1024, hop=256, cpu=True):
@@ -436,7 +461,8 @@ def config5_dry_run(a, ctx):
                           "roofline": {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
                                        "kernel_ms_per_file_alone_min_max": None},
                           "cpu_baseline": None,
-                          "cpu_baseline_note": "timed on the N = 1 lines only (python bench.py, python bench.py --config5): the contract's rule"}),
+                          "cpu_baseline_note": "timed on the N = 1 lines only, with --full (python bench.py --full, python bench.py "
+                                               "--config5 --full): the contract's rule"}),
               flush=True)
     ctx.close()
 
@@ -587,11 +613,12 @@ def config5_batch(a, ctx):
                                  "names; what limits the kernel is VALU issue (the N = 1 line carries the per-kernel HIP-event "
                                  "timing, PMC traffic and the VALU roofline)"},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(a.sr, a.nt)          # (rank 0 at N = 1 only: the contract)
         else:
             res["cpu_baseline"] = None
-            res["cpu_baseline_note"] = "timed on the N = 1 lines only (python bench.py, python bench.py --config5): the contract's rule"
+            res["cpu_baseline_note"] = ("timed on the N = 1 lines only, with --full (python bench.py --full, python bench.py "
+                                        "--config5 --full): the contract's rule")
         if e2e is not None:
             v_e, n1_e, dt_e = e2e
             res["value_e2e"] = round(v_e, 3)
@@ -632,7 +659,14 @@ def main():
     ap.add_argument("--n1-e2e-files", type=int, default=24, help="files of the one-GPU base of the host-gather leg")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-gather leg of the config-5 mode")
     ap.add_argument("--dry-run", action="store_true", help="config-5 flow with a sleep per file instead of GPU work (CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline, the secondary workloads and the oracle parity "
+                         "windows (a plain run times the headline workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (a fixed, seeded sample of it, at most 48 MiB) as DIR/*.npy")
     a = ap.parse_args()
+    if a.dump_outputs is not None and (a.gpus > 1 or a.config5 or a.dry_run):
+        ap.error("--dump-outputs: the single-file mode only (--gpus 1 without --config5 / --dry-run)")
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if a.gpus > 1 and env_world == 0:
         sys.exit(_launch_ranks(a))                     # start the N ranks ourselves; rank 0 of the child run prints the line
@@ -740,7 +774,8 @@ def main():
         # reference point outside the timed region: K_sinc with the GPU to itself (no plan underneath), launched back to
         # back like the timed steps -- 30 launches, the last 20 timed.  (A single launch on an idle GPU, which is what this
         # measured until r03, runs 8-10 % slower: the clocks have to come up first.  Sustained, the kernel sits at the
-        # board's power limit, ~1.37 kW at 2.0-2.2 GHz: tools/exp/sustained_clock.py.)
+        # board's power limit, ~1.37 kW at 2.0-2.2 GHz: tools/exp/sustained_clock.py.)  A plain run keeps these launches too:
+        # ~0.15 s of K_sinc, and the warm GPU the timed region has always started from.
         alone = []
         e0, e1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float(0)
         _lib.check(L.par_event_create(ctypes.byref(e0)))
@@ -819,6 +854,8 @@ def main():
             sinc_launches.append(1)
             L.par_event_destroy(e0)
             L.par_event_destroy(e1)
+    if a.dump_outputs is not None:                     # `out` holds the last timed step's output (every step writes all of it)
+        dump_outputs(a.dump_outputs, out, int(len_out.value))
 
     if rank == 0:
         ms_step_mean = dt / a.steps * 1e3
@@ -912,7 +949,7 @@ def main():
                                     "running_digest": digest, "stale": vp.get("source_digest") != digest}
         except Exception:
             pass
-        if world == 1:
+        if a.full and world == 1:
             res["secondary"] = stft_secondary(sig, dev, cpu=not a.no_cpu_baseline)
             res["secondary_config4"] = heal_secondary(dev)
             if hasattr(L, "par_varispeed_fused_stereo_f32"):        # absent only in an older build under PAR_HIP_LIB
@@ -929,9 +966,9 @@ def main():
                 res["archive_note"] = ("config-5 archive rate of ONE GPU (10-min 192 kHz stereo files through the batch driver, the "
                                        "code path of --gpus N > 1): the base of the 1/2/4/8-GPU curve is archive_value here and "
                                        "n1_same_workload_value in the N > 1 lines, never this line's `value`")
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(a.sr, a.nt)
-        if not a.no_parity and world == 1:
+        if a.full and not a.no_parity and world == 1:
             torch.cuda.synchronize()
             res["parity_checked"] = parity_windows(out, sig, st, spd, n_in, int(len_out.value), a.nt)
         print(json.dumps(res), flush=True)

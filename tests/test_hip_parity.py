@@ -1931,13 +1931,13 @@ def test_library_is_reentrant_across_host_threads_and_streams(par):
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the contract's keys, a roofline and a cpu_baseline object."""
+    """bench.py --full prints ONE JSON line with the contract's keys, a roofline and a cpu_baseline object."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--seconds", "20", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--seconds", "20", "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1966,6 +1966,63 @@ def test_bench_contract_line():
         assert rl["source"]["kernel_symbols"] == rl["kernel_symbols"]
     if "roofline_valu" in r:
         assert r["roofline_valu"]["kernel_symbols"] == rl["kernel_symbols"]
+
+
+def test_bench_plain_line_and_dump_outputs(par, tmp_path):
+    """A plain bench.py run times the headline workload only (the CPU baseline, the secondary workloads and the oracle windows
+    are --full's) and runs exactly --steps timed steps; --dump-outputs writes the last timed step's output, the same in two
+    runs, and that output is the resampler's: windows of it against the C oracle on the bench's own seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from oracle import oracle_c as C
+    from pyaudiorestoration_amd import _dev, _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sr, dur = 192000, 20.0
+    lines = []
+    for k in range(2):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--seconds", str(dur), "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / f"d{k}")], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1
+        lines.append(json.loads(got[0]))
+    r = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in r, key
+    for key in ("cpu_baseline", "secondary", "secondary_config4", "secondary_config5", "secondary_nt50", "archive_value", "parity_checked"):
+        assert key not in r, key
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "Msamples/s"
+    n_out = r["config"]["samples_out_per_gpu"]
+    files = {}
+    for k in range(2):
+        d = tmp_path / f"d{k}"
+        names = sorted(os.listdir(d))
+        assert names == ["output.npy", "output_index.npy", "output_len.npy"], names
+        assert sum(os.path.getsize(d / f) for f in names) <= 64 << 20
+        files[k] = {f[:-4]: np.load(d / f) for f in names}
+        assert all(v.dtype in (np.float32, np.float64) for v in files[k].values())
+    for name in files[0]:
+        assert np.array_equal(files[0][name], files[1][name]), name
+    y, idx = files[0]["output"], files[0]["output_index"]
+    assert int(files[0]["output_len"][0]) == n_out and np.array_equal(idx, np.arange(n_out)) and y.dtype == np.float32
+    # the same inputs bench.py synthesises (rank 0), the oracle's positions and sinc on windows of the dumped output
+    t = par.torch
+    L = _lib.lib()
+    n = int(sr * dur)
+    m = int(dur * sr / 256)
+    sig_t = t.empty(n, dtype=t.float32, device="cuda")
+    st_t = t.empty(m, dtype=t.float64, device="cuda")
+    sp_t = t.empty(m, dtype=t.float64, device="cuda")
+    _lib.check(L.par_synth_signal_f32(0, _dev.ptr(sig_t), 0, n, float(sr), 0x5EED, _dev.stream_ptr(0)))
+    _lib.check(L.par_synth_speed_curve_f64(0, _dev.ptr(st_t), _dev.ptr(sp_t), m, dur, float(sr), 0.01, 0.55, 0.7, _dev.stream_ptr(0)))
+    ref_pos, _ = C.speed_to_pos(st_t.cpu().numpy(), sp_t.cpu().numpy(), n)
+    sig = sig_t.cpu().numpy()
+    assert len(ref_pos) == n_out
+    W = 2000
+    for i in [int(v) for v in np.linspace(0, n_out - W - 1, 8)]:
+        assert relerr(y[i:i + W], C.sinc(ref_pos[i:i + W], sig, 32)) < TOL, i
 
 
 def test_headless_cli_respeed_and_resample(par, golden, tmp_path):
