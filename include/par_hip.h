@@ -427,6 +427,42 @@ int par_sosfiltfilt_batch_f64(int device, const double* sos, const double* zi, i
                               int64_t x_stride, int n_sig, int64_t n, int64_t padlen, double* work, int64_t work_len, double* y,
                               int64_t y_stride, void* stream);
 
+/* ---- Spectral Expander (expander_gui.py) and time-averaged spectra (util/spectrum_flat.py), ABI 107 ------------------------ */
+/* Band dB straight out of the STFT: out[f] (DEVICE f64[par_stft_frames(n, n_fft, hop)]) = mean over b in [bin_l, bin_u) of
+ * 20 log10(|X_f[b]| / sqrt(n_fft) + 1e-7), the magnitude being the float32 value par_stft_f32 mode 1 writes and the log and
+ * the sum float64 -- expander_gui.py:126-133 (nanmean of the band rows of spectrum_from_audio_stereo) without the
+ * spectrogram.  Signal, window and frames as par_stft_f32 (x_stride: a channel of an interleaved file; reflect padding,
+ * repeated for signals shorter than n_fft / 2).  n_fft*zeropad a power of two in [16, 16384], else PAR_ERR_UNSUPPORTED
+ * (the host layer composes par_stft_big_f32 mode 1 and par_band_mean_db_f32 above); 0 <= bin_l < bin_u <= bins. */
+int par_stft_band_db_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, int zeropad,
+                         const float* window, int bin_l, int bin_u, double* out, void* stream);
+/* acc[b] += sum over f < n_frames of 20 log10(mag[f * mag_pitch + b]) for b < bins (DEVICE f32 frame-major magnitudes as
+ * par_stft_f32 mode 1 writes them; mag_pitch 0 = bins; DEVICE f64 acc[bins]).  Called once per frame chunk; the caller divides
+ * by the total frame count (spectrum_flat.py:20-24 temporal mean).  Fixed summation order, no atomics. */
+int par_mean_db_frames_f32(int device, const float* mag, int64_t n_frames, int64_t bins, int64_t mag_pitch, double* acc,
+                           void* stream);
+/* scipy.ndimage.uniform_filter1d(in[r], size, mode="nearest") for each of `rows` rows of n float64 (DEVICE, row-major,
+ * out != in); size odd, any value (windows longer than the row repeat the edge values).  Compensated window sums: within
+ * about an ulp of the exact window mean (expander_gui.py:134). */
+int par_uniform_filter_nearest_f64(int device, const double* in, int64_t rows, int64_t n, int size, double* out, void* stream);
+/* Expander gain (expander_gui.py:184-197), channel c < n_ch of the interleaved signal sig[i * sig_stride + c] (DEVICE f32):
+ *   fac[j] = 10^((clip_upper - clip(curve[c * frames + j], clip_lower, clip_upper)) / 20)     (DEVICE f64 curve[n_ch][frames])
+ *   g      = np.interp(i, j * hop, fac)   (end values held outside the frames)
+ *   boosted = float64(sig) * g
+ * out_f64 == NULL: out_f32[i * out_stride + c] = float32(boosted)  (the transition == 0 branch)
+ * else:            out_f64[c * n + i] = boosted, out_f64[(n_ch + c) * n + i] = float64(sig)   (DEVICE f64[2][n_ch][n]: the
+ *                  high-pass and low-pass inputs of the transition branch) */
+int par_expand_gain_f32(int device, const float* sig, int64_t sig_stride, int n_ch, int64_t n, const double* curve,
+                        int64_t frames, int hop, double clip_lower, double clip_upper, float* out_f32, int64_t out_stride,
+                        double* out_f64, void* stream);
+/* out[i * out_stride + c] = float32(a[c * n + i] + b[c * n + i])  (DEVICE; lp + hp of expander_gui.py:201, summed in float64) */
+int par_sum_rows_f64_f32(int device, const double* a, const double* b, int n_ch, int64_t n, float* out, int64_t out_stride,
+                         void* stream);
+/* units.normalize (util/units.py:32-39) in place: d /= max|d| over d[0 .. count) (DEVICE f32), NaN propagating like np.max.
+ * scratch: DEVICE, PAR_NORMALIZE_SCRATCH_BYTES.  Deterministic (max is order-free; the division is float32). */
+#define PAR_NORMALIZE_SCRATCH_BYTES 4096
+int par_normalize_f32(int device, float* d, int64_t count, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,7 +102,14 @@ SIGNATURES = {
     "par_track_corr_work_len": (c_i64, [c_i64, c_int]),
     "par_track_corr_f64": (c_int, [c_int, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_int, c_dbl, c_dbl, c_vp, c_vp,
                                    c_vp, c_vp]),
+    "par_stft_band_db_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
+    "par_mean_db_frames_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "par_uniform_filter_nearest_f64": (c_int, [c_int, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
+    "par_expand_gain_f32": (c_int, [c_int, c_vp, c_i64, c_int, c_i64, c_vp, c_i64, c_int, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp]),
+    "par_sum_rows_f64_f32": (c_int, [c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp]),
+    "par_normalize_f32": (c_int, [c_int, c_vp, c_i64, c_vp, c_vp]),
 }
+NORMALIZE_SCRATCH_BYTES = 4096      # PAR_NORMALIZE_SCRATCH_BYTES
 
 _lib = None
 

@@ -10,6 +10,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli resample --speed 1.015 tape.wav           # constant correction
     python -m pyaudiorestoration_amd.cli tapesync --project take.tapesync take2.flac
     python -m pyaudiorestoration_amd.cli heal --project tape.drop tape.flac
+    python -m pyaudiorestoration_amd.cli expand --channels L+R --clip -120,-85 tape.wav     # Spectral Expander -> tape_decompressed.wav
 """
 import argparse
 import json
@@ -27,7 +28,7 @@ def _worker(dev, jobs, args, results):
     release the GIL) on a helper thread while the current one is on the GPU."""
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    from . import _dev, io_ops, pipeline, resampling
+    from . import _dev, expander, io_ops, pipeline, resampling
     torch.cuda.set_device(dev)
 
     def take():
@@ -54,6 +55,12 @@ def _worker(dev, jobs, args, results):
                     results.append((path, None))
                     continue
                 signal, sr, ch = pending.result()
+                if args.cmd == "expand":
+                    expander.expand_file(path, args.channels, args.fft_size, args.hop, args.band[0], args.band[1], args.smoothing,
+                                         args.clip[0], args.clip[1], args.transition, args.order, args.suffix, device=dev,
+                                         signal_data=(signal, sr, ch))
+                    results.append((path, None))
+                    continue
                 quality = 50 if args.quality is None else args.quality          # the GUI's default (util/widgets.py:998-1000)
                 suffix = args.suffix or ""
                 if args.cmd == "respeed":
@@ -102,6 +109,19 @@ def main(argv=None):
         p.add_argument("--suffix", default=None, help="output suffix; default: the project's, else none")
         p.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
         p.add_argument("files", nargs="+")
+    pair = lambda s: [float(v) for v in s.split(",")]
+    e = sub.add_parser("expand", help="Spectral Expander: boost quiet passages by the level of a noise-floor band")
+    e.add_argument("--channels", default="L+R", choices=("L+R", "L", "R", "Mean"), help="which channels are analysed")
+    e.add_argument("--band", type=pair, default=[13000.0, 17000.0], help="LO,HI (Hz): the noise-floor band")
+    e.add_argument("--clip", type=pair, default=[-120.0, -85.0], help="LO,HI (dB): gain boundaries of the noise floor")
+    e.add_argument("--smoothing", type=float, default=0.11, help="smoothing window (s)")
+    e.add_argument("--transition", type=int, default=0, help="high-pass transition (Hz); 0: the whole band is expanded")
+    e.add_argument("--order", type=int, default=1, help="order of the transition filters")
+    e.add_argument("--fft-size", type=int, default=512)
+    e.add_argument("--hop", type=int, default=64)
+    e.add_argument("--suffix", default="_decompressed", help="output suffix")
+    e.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
+    e.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s")
     import torch

@@ -16,6 +16,7 @@
 // algorithmic minimum: each input sample is fetched from HBM once (neighbouring frames hit L2) and
 // each output bin is written once; magnitude never round-trips a complex spectrogram.
 #include "par_common.h"
+#include "db_math.h"
 #include <math.h>
 #include <map>
 #include <set>
@@ -247,7 +248,10 @@ struct FftGeom {
   static constexpr int FrameLds = H + H / 8 + 8;                // padded float2 slots per frame
 };
 
-// MODE 0: complex spectrum, 1: magnitude |X| + 1e-7.  UNIT: the signal is contiguous (x_stride == 1): no 64-bit stride
+// MODE 0: complex spectrum, 1: magnitude |X| + 1e-7, 2: band dB -- out[f] (float64, `out` reinterpreted) = mean over
+// b in [bin_l, bin_u) of 20 log10(the float32 magnitude mode 1 writes), with the band packed into `pitch` as
+// bin_l | bin_u << 32 (the kernel's parameter list, and so the code of modes 0 and 1, stays as it was).  Mode 2 writes
+// one float64 per frame: no spectrogram reaches HBM, and only the band's bins take a log.  UNIT: the signal is contiguous (x_stride == 1): no 64-bit stride
 // multiply per sample and the two samples of a packed point arrive in one 8-byte load.
 template <int LOGH, int MODE, bool UNIT>
 __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __restrict__ x, int64_t n, int64_t x_stride_arg,
@@ -315,8 +319,10 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __
   for (int i = 0; i < P; ++i) pw[i] = post[j + i * T];
   pw[P] = post[H / 2];
   fft_core<LOGH>(v, X, j, tw);
-  if (!live) return;
+  if (mode != 2 && !live) return;         // mode 2 keeps every lane to the frame reduction (a workgroup barrier for T > 64)
   const float hs = 0.5f * scale;
+  const int band_l = (int)(pitch & 0xffffffffll), band_u = (int)(pitch >> 32);    // mode 2 only
+  double band_acc = 0.0;
   // PAR_STFT_STORE (experiment switch): 0 streaming (nontemporal) stores straight from the registers; 1 plain stores;
   // 3 one-wave-per-frame sizes stage the row in the wave's own LDS and write it with 16-byte aligned stores
   constexpr bool kRowStage = (PAR_STFT_STORE == 3) && T == kWave;
@@ -329,6 +335,9 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __
     // 2 % on the config-4 chain).
     if constexpr (mode == 0) {
       reinterpret_cast<float2*>(out)[fr * pitch + k] = make_float2(re * hs, im * hs);
+    } else if constexpr (mode == 2) {
+      if (k >= band_l && k < band_u)
+        band_acc += 20.0 * log10_pos((double)fmaf(__builtin_amdgcn_sqrtf(fmaf(re, re, im * im)), hs, 1e-7f));
     } else {
       // v_sqrt_f32 itself (1 ulp): the correctly rounded sqrtf costs 16 instructions per bin, mostly compares and selects
       const float mag = fmaf(__builtin_amdgcn_sqrtf(fmaf(re, re, im * im)), hs, 1e-7f);
@@ -374,6 +383,23 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __
     }
     if (j < a0 - e0) __builtin_nontemporal_store(Mg[j], out + e0 + j);
     if (j < e1 - a1) __builtin_nontemporal_store(Mg[a1 - e0 + j], out + a1 + j);
+  }
+  if constexpr (mode == 2) {
+    // the frame's T lanes sum in a fixed order: xor butterflies inside the wave, then (T > 64) the waves' partials in
+    // wave order from LDS beside the frames
+    constexpr int kLanes = T < kWave ? T : kWave;
+#pragma unroll
+    for (int o = kLanes / 2; o > 0; o >>= 1) band_acc += __shfl_xor(band_acc, o, kWave);
+    if constexpr (T > kWave) {
+      double* part = reinterpret_cast<double*>(lds + G::Frames * G::FrameLds) + f * (T / kWave);
+      if ((j & (kWave - 1)) == 0) part[j / kWave] = band_acc;
+      __syncthreads();
+      if (j == 0) {
+        band_acc = part[0];
+        for (int w = 1; w < T / kWave; ++w) band_acc += part[w];
+      }
+    }
+    if (live && j == 0) reinterpret_cast<double*>(out)[fr] = band_acc / (double)(band_u - band_l);
   }
 }
 
@@ -1285,6 +1311,66 @@ int par_stft_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_
   }
 #undef PAR_STFT_LAUNCH
 #undef PAR_STFT_LAUNCH_MU
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+// Band dB straight out of the register-path transform (k_stft mode 2): out[f] = mean over b in [bin_l, bin_u) of
+// 20 log10(|X_f[b]| / sqrt(n_fft) + 1e-7), float64, one value per frame of par_stft_frames(n, n_fft, hop).
+int par_stft_band_db_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, int zeropad,
+                         const float* window, int bin_l, int bin_u, double* out, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(x && window && out, PAR_ERR_ARG, "par_stft_band_db_f32: null pointer");
+  PAR_REQUIRE(n >= 1 && x_stride >= 1 && hop >= 1 && zeropad >= 1 && n_fft >= 2, PAR_ERR_ARG, "par_stft_band_db_f32: bad sizes");
+  const int64_t M64 = (int64_t)n_fft * zeropad;
+  PAR_REQUIRE(0 <= bin_l && bin_l < bin_u && (int64_t)bin_u <= M64 / 2 + 1, PAR_ERR_ARG,
+              "par_stft_band_db_f32: empty or out-of-range band [%d, %d) of %lld bins", bin_l, bin_u, (long long)(M64 / 2 + 1));
+  PAR_REQUIRE(M64 >= 16 && M64 <= 16384 && (M64 & (M64 - 1)) == 0 && (n_fft % 2) == 0, PAR_ERR_UNSUPPORTED,
+              "par_stft_band_db_f32: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)M64);
+  const int M = (int)M64, H = M / 2;
+  PAR_HIP_CHECK(hipSetDevice(device));
+  Twiddles tw;
+  int rc = get_twiddles(device, M, &tw);
+  if (rc != PAR_OK) return rc;
+  const int64_t n_frames = par_stft_frames(n, n_fft, hop);
+  const float scale = (float)(1.0 / sqrt((double)n_fft));
+  const int64_t band = (int64_t)bin_l | ((int64_t)bin_u << 32);
+  float* outf = reinterpret_cast<float*>(out);
+#define PAR_BAND_LAUNCH_U(LH, UN)                                                                                       \
+  hipLaunchKernelGGL((k_stft<LH, 2, UN>), dim3((unsigned)(ceil_div(ceil_div(n_frames, FftGeom<LH>::Frames), 8) * 8)),   \
+                     dim3(FftGeom<LH>::Threads),                                                                         \
+                     (size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2) +                              \
+                         (size_t)FftGeom<LH>::Threads / kWave * sizeof(double),                                          \
+                     as_stream(stream), x, n, x_stride, n_fft, hop, window, tw.w, tw.post, outf, n_frames, scale, band)
+#define PAR_BAND_LAUNCH(LH)                        \
+  do {                                             \
+    if (x_stride == 1) PAR_BAND_LAUNCH_U(LH, true); \
+    else PAR_BAND_LAUNCH_U(LH, false);              \
+  } while (0)
+  switch (ilog2(H)) {
+    case 3: PAR_BAND_LAUNCH(3); break;
+    case 4: PAR_BAND_LAUNCH(4); break;
+    case 5: PAR_BAND_LAUNCH(5); break;
+    case 6: PAR_BAND_LAUNCH(6); break;
+    case 7: PAR_BAND_LAUNCH(7); break;
+    case 8: PAR_BAND_LAUNCH(8); break;
+    case 9: PAR_BAND_LAUNCH(9); break;
+    case 10: PAR_BAND_LAUNCH(10); break;
+    case 11: PAR_BAND_LAUNCH(11); break;
+    case 12: PAR_BAND_LAUNCH(12); break;
+    case 13: {
+      constexpr int kLds13 = FftGeom<13>::Frames * FftGeom<13>::FrameLds * (int)sizeof(float2) + FftGeom<13>::Threads / kWave * 8;
+      for (const void* fn : {reinterpret_cast<const void*>(&k_stft<13, 2, true>), reinterpret_cast<const void*>(&k_stft<13, 2, false>)}) {
+        const int rc2 = raise_dynamic_lds(fn, kLds13, device);
+        if (rc2 != PAR_OK) return rc2;
+      }
+      PAR_BAND_LAUNCH(13);
+      break;
+    }
+    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_band_db_f32: unsupported size");
+  }
+#undef PAR_BAND_LAUNCH
+#undef PAR_BAND_LAUNCH_U
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }
