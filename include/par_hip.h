@@ -463,6 +463,33 @@ int par_sum_rows_f64_f32(int device, const double* a, const double* b, int n_ch,
 #define PAR_NORMALIZE_SCRATCH_BYTES 4096
 int par_normalize_f32(int device, float* d, int64_t count, void* scratch, void* stream);
 
+
+/* ---- renoiser noise-floor gate (renoiser_gui.py:239-345), ABI 108 ------------------------------------------------------------ */
+/* get_mask_fac + X * fac of renoiser_gui.py:273-278, 312-313 in place on a frame-major complex64 spectrogram (DEVICE
+ * c64 spec[n_frames][pitch], the layout par_stft_f32 mode 0 and par_stft_big_f32 mode 0 write; pitch 0 = bins): bin b of every
+ * frame passes unchanged when float32(hypot(re, im)) + 1e-7f >= cutoff[b] (DEVICE f32[bins]), else both parts are multiplied
+ * by `low` (float32(10^(gain/20))) as numpy multiplies complex64 by float32.  |X| is the float32 value numpy's np.abs gives
+ * for complex64 (its SIMD loop: larger * sqrt(fma(r, r, 1)), r = smaller / larger); the cutoffs come from the float64
+ * thresholds through renoiser.gate_cutoffs (a NaN cutoff gates the bin).  The result equals numpy's on the same spectrum bit
+ * for bit. */
+int par_gate_spectrum_f32(int device, float* spec, int64_t n_frames, int64_t bins, int64_t pitch, const float* cutoff, float low,
+                          void* stream);
+/* Fused renoiser apply (renoiser_gui.py:296-319), one launch for n_ch channels: channel c < n_ch of the interleaved signal
+ * x[i * x_stride + c] (DEVICE f32, i < n) is zero-extended to n + n_fft/2 (fix_length), transformed (blackmanharris or any
+ * `window`, DEVICE f32[n_fft]; reflect padding of the extended length, frames and scaling of par_stft_f32 mode 0), gated as
+ * par_gate_spectrum_f32 does, inverse transformed and overlap-added with the window-sum-square normalisation of
+ * par_istft_f32 (length n), and written to y[i * y_stride + c] (DEVICE f32).  No spectrogram reaches HBM.  n_fft a power of
+ * two in [16, 8192] and 1 <= hop <= n_fft, else PAR_ERR_UNSUPPORTED (compose par_stft_*, par_gate_spectrum_f32 and
+ * par_istft_f32).  Bins hold the same gate decisions as par_gate_spectrum_f32 on par_stft_f32's spectrum. */
+int par_gate_stft_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_ch, int n_fft, int hop, const float* window,
+                      const float* cutoff, float low, float* y, int64_t y_stride, void* stream);
+/* Frames par_gate_stft_f32 transforms per channel (each forward and back; host only, for reporting the streaming form's
+ * redundant-frame share); 0 when the size is unsupported. */
+int64_t par_gate_stft_transformed_frames(int64_t n, int n_fft, int hop);
+/* acc[b] += sum over f < n_frames of mag[f * mag_pitch + b] (float64, the fixed order of par_mean_db_frames_f32): the
+ * numerator of the selection profile np.average(mag[:, f0:f1], axis=1) (renoiser_gui.py:340). */
+int par_mean_mag_frames_f32(int device, const float* mag, int64_t n_frames, int64_t bins, int64_t mag_pitch, double* acc,
+                            void* stream);
 #ifdef __cplusplus
 }
 #endif

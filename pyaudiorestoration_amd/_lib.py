@@ -108,6 +108,10 @@ SIGNATURES = {
     "par_expand_gain_f32": (c_int, [c_int, c_vp, c_i64, c_int, c_i64, c_vp, c_i64, c_int, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp]),
     "par_sum_rows_f64_f32": (c_int, [c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp]),
     "par_normalize_f32": (c_int, [c_int, c_vp, c_i64, c_vp, c_vp]),
+    "par_gate_spectrum_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_float, c_vp]),
+    "par_gate_stft_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_float, c_vp, c_i64, c_vp]),
+    "par_gate_stft_transformed_frames": (c_i64, [c_i64, c_int, c_int]),
+    "par_mean_mag_frames_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
 }
 NORMALIZE_SCRATCH_BYTES = 4096      # PAR_NORMALIZE_SCRATCH_BYTES
 

@@ -11,6 +11,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli tapesync --project take.tapesync take2.flac
     python -m pyaudiorestoration_amd.cli heal --project tape.drop tape.flac
     python -m pyaudiorestoration_amd.cli expand --channels L+R --clip -120,-85 tape.wav     # Spectral Expander -> tape_decompressed.wav
+    python -m pyaudiorestoration_amd.cli renoise --noise hiss.wav tape.wav                  # renoiser -> "tape fft=2048.wav"
 """
 import argparse
 import json
@@ -28,7 +29,7 @@ def _worker(dev, jobs, args, results):
     release the GIL) on a helper thread while the current one is on the GPU."""
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    from . import _dev, expander, io_ops, pipeline, resampling
+    from . import _dev, expander, io_ops, pipeline, renoiser, resampling
     torch.cuda.set_device(dev)
 
     def take():
@@ -61,6 +62,11 @@ def _worker(dev, jobs, args, results):
                                          signal_data=(signal, sr, ch))
                     results.append((path, None))
                     continue
+                if args.cmd == "renoise":
+                    renoiser.renoise_file(path, args.noise, args.select, args.fft, args.overlap, args.gain, args.overhead, args.curve,
+                                          args.channels, device=dev, signal_data=(signal, sr, ch))
+                    results.append((path, None))
+                    continue
                 quality = 50 if args.quality is None else args.quality          # the GUI's default (util/widgets.py:998-1000)
                 suffix = args.suffix or ""
                 if args.cmd == "respeed":
@@ -83,7 +89,7 @@ def _worker(dev, jobs, args, results):
                 results.append((path, e))
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(prog="pyaudiorestoration_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
     a = sub.add_parser("respeed", help="trace a pilot tone / hum and remove wow & flutter")
@@ -122,7 +128,25 @@ def main(argv=None):
     e.add_argument("--suffix", default="_decompressed", help="output suffix")
     e.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
     e.add_argument("files", nargs="+")
-    args = ap.parse_args(argv)
+    ints = lambda s: [int(v) for v in s.split(",") if v != ""]
+    curve = lambda s: [[float(v) for v in p.split(":")] for p in s.split(",")]
+    r = sub.add_parser("renoise", help="renoiser: gate (or boost) every STFT bin at or under a noise profile + gain + overhead")
+    prof = r.add_mutually_exclusive_group()
+    prof.add_argument("--noise", default=None, help="noise recording at the file's sample rate (its first channel is the profile)")
+    prof.add_argument("--select", type=pair, default=None, help="T0,T1 (s): the profile is this time range of channel 0")
+    r.add_argument("--fft", type=int, default=2048, help="FFT size")
+    r.add_argument("--overlap", type=int, default=4, help="hop = fft / overlap")
+    r.add_argument("--gain", type=float, default=12.0, help="dB applied to every bin at or under the final profile")
+    r.add_argument("--overhead", type=float, default=3.0, help="dB added to the profile")
+    r.add_argument("--curve", type=curve, default=None, help="F:DB,... control curve (default 1:0,<sr/2>:0)")
+    r.add_argument("--channels", type=ints, default=None, help="channel numbers, e.g. 0,1 (default: all)")
+    r.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
+    r.add_argument("files", nargs="+")
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s")
     import torch
     if not torch.cuda.is_available():

@@ -19,6 +19,8 @@ namespace par {
 // thread (bin lane, frame lane): 64 consecutive bins per workgroup (coalesced rows), 4 frame lanes that take every 4th frame;
 // the four partials meet in LDS in lane order -- the sum does not depend on the launch
 constexpr int kMeanBins = 64, kMeanLanes = 4;
+// kDb: the summand is 20 log10(mag) (the temporal mean of dB); otherwise mag itself (the renoiser's selection profile, ABI 108)
+template <bool kDb>
 __global__ void __launch_bounds__(kMeanBins * kMeanLanes) k_mean_db_frames(const float* __restrict__ mag, int64_t n_frames, int64_t bins,
                                                                            int64_t pitch, double* __restrict__ acc) {
   __shared__ double part[kMeanLanes][kMeanBins];
@@ -26,7 +28,7 @@ __global__ void __launch_bounds__(kMeanBins * kMeanLanes) k_mean_db_frames(const
   const int64_t b = (int64_t)blockIdx.x * kMeanBins + bl;
   double s = 0.0;
   if (b < bins)
-    for (int64_t f = fl; f < n_frames; f += kMeanLanes) s += 20.0 * log10_pos((double)mag[f * pitch + b]);
+    for (int64_t f = fl; f < n_frames; f += kMeanLanes) s += kDb ? 20.0 * log10_pos((double)mag[f * pitch + b]) : (double)mag[f * pitch + b];
   part[fl][bl] = s;
   __syncthreads();
   if (fl == 0 && b < bins) {
@@ -161,8 +163,26 @@ extern "C" int par_mean_db_frames_f32(int device, const float* mag, int64_t n_fr
   PAR_REQUIRE(ceil_div(bins, kMeanBins) <= 0x7fffffff, PAR_ERR_UNSUPPORTED, "par_mean_db_frames_f32: too many bins");
   if (n_frames == 0) return PAR_OK;
   PAR_HIP_CHECK(hipSetDevice(device));
-  hipLaunchKernelGGL(k_mean_db_frames, dim3((unsigned)ceil_div(bins, kMeanBins)), dim3(kMeanBins * kMeanLanes), 0, as_stream(stream), mag,
+  hipLaunchKernelGGL(k_mean_db_frames<true>, dim3((unsigned)ceil_div(bins, kMeanBins)), dim3(kMeanBins * kMeanLanes), 0, as_stream(stream), mag,
                      n_frames, bins, mag_pitch ? mag_pitch : bins, acc);
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+// renoiser_gui.py:327-345 (selection profile): acc[b] += sum over f < n_frames of mag[f * mag_pitch + b], float64, the same fixed
+// order as par_mean_db_frames_f32
+extern "C" int par_mean_mag_frames_f32(int device, const float* mag, int64_t n_frames, int64_t bins, int64_t mag_pitch, double* acc,
+                                       void* stream) {
+  using namespace par;
+  PAR_REQUIRE(mag && acc, PAR_ERR_ARG, "par_mean_mag_frames_f32: null pointer");
+  PAR_REQUIRE(n_frames >= 0 && bins >= 1 && (mag_pitch == 0 || mag_pitch >= bins), PAR_ERR_ARG,
+              "par_mean_mag_frames_f32: bad sizes (frames %lld, bins %lld, pitch %lld)", (long long)n_frames, (long long)bins,
+              (long long)mag_pitch);
+  PAR_REQUIRE(ceil_div(bins, kMeanBins) <= 0x7fffffff, PAR_ERR_UNSUPPORTED, "par_mean_mag_frames_f32: too many bins");
+  if (n_frames == 0) return PAR_OK;
+  PAR_HIP_CHECK(hipSetDevice(device));
+  hipLaunchKernelGGL(k_mean_db_frames<false>, dim3((unsigned)ceil_div(bins, kMeanBins)), dim3(kMeanBins * kMeanLanes), 0,
+                     as_stream(stream), mag, n_frames, bins, mag_pitch ? mag_pitch : bins, acc);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }

@@ -1226,6 +1226,234 @@ static inline bool istft_is_fused(int n_fft, int hop) {
   return hop >= 1 && n_fft <= PAR_ISTFT_FUSE_MAX && istft_fused_lds_any(n_fft, hop) <= 64 * 1024;
 }
 
+// ---- renoiser gate (renoiser_gui.py:273-319, ABI 108) ------------------------------------------------------------------------
+// get_mask_fac: a bin passes unchanged when float32(20 log10(float32(|X| + 1e-7))) > final[k], else it is multiplied by the
+// float32 factor 10^(gain/20).  float32 20 log10 is monotone, so the host turns each threshold into one float32 magnitude
+// cutoff c[k] (renoiser.gate_cutoffs): "passes" is then |X| + 1e-7 >= c[k] -- no transcendental per bin, and a NaN cutoff
+// gates every bin.  |X| is the float32 value numpy's np.abs gives for complex64, which its SIMD loop computes as
+// larger * sqrt(fma(r, r, 1)), r = smaller / larger, every step a correctly rounded float32 operation (not hypotf: that
+// differs from numpy in about a quarter of all bins by an ulp, and v_sqrt_f32 of mode 1 by another).  Contraction off: the
+// product and the + 1e-7 round separately, as numpy's do.
+__device__ __forceinline__ float gate_mag(float re, float im) {
+#pragma clang fp contract(off)
+  const float ar = fabsf(re), ai = fabsf(im);
+  if (ar == __builtin_inff() || ai == __builtin_inff()) return __builtin_inff();
+  if (ar != ar || ai != ai) return __builtin_nanf("");
+  const float larger = fmaxf(ar, ai), smaller = fminf(ar, ai);
+  const float r = larger == 0.0f ? 0.0f : __fdiv_rn(smaller, larger);
+  const float mag = __fsqrt_rn(fmaf(r, r, 1.0f)) * larger;
+  return mag + 1e-7f;
+}
+// X * fac as numpy multiplies complex64 by a float32 (fac becomes fac + 0i): the products with the zero imaginary part are kept
+// -- they decide the signs of zero parts (and NaNs from infinite parts) exactly as numpy's do, a passing bin included
+__device__ __forceinline__ float2 gate_bin(float2 v, float cut, float low) {
+  const float f = gate_mag(v.x, v.y) >= cut ? 1.0f : low;
+  return make_float2(v.x * f - v.y * 0.0f, v.x * 0.0f + v.y * f);
+}
+
+__global__ __launch_bounds__(256) void k_gate_spectrum(float2* __restrict__ spec, int64_t n_frames, int64_t bins, int64_t pitch,
+                                                       const float* __restrict__ cutoff, float low) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= bins) return;
+  const float cut = cutoff[b];
+  for (int64_t f = blockIdx.y; f < n_frames; f += gridDim.y) {
+    float2* p = spec + f * pitch + b;
+    *p = gate_bin(*p, cut, low);
+  }
+}
+
+// Fused gate: signal -> forward real FFT (K_stft mode 0's operations) -> gate -> irfft (K_istft's) -> window-sum-square
+// overlap-add -> output, one launch, no spectrogram in HBM.  The signal is the reference's fix_length(x, n + n_fft/2): the
+// appended zeros and the reflect boundary of that padded length are folded into the gather (no padded copy).
+// Streaming form: a workgroup owns a run of NF = Frames * rounds consecutive frames and walks it Frames at a time.  Each
+// round's frames go forward, through the gate (in registers: a lane holds the bin pairs (k, H - k) after the untangle), back
+// (one LDS exchange forms the inverse input) and into an LDS ring of R floats; the ring positions every covering frame has
+// reached are normalised, stored and cleared.  Only the first s - 1 frames of a run (s = ceil(n_fft / hop)) are also
+// transformed by the neighbouring run.  Every sample sums its frames in ascending order.
+template <int LOGH>
+struct GateGeom {
+  using G = FftGeom<LOGH>;
+  static int rounds(int s) { return (int)ceil_div(12 * (int64_t)s, G::Frames); }          // (s - 1) / NF < 1/12 redundant
+  static int ring(int hop) {
+    int r = 1;
+    while (r < 2 * G::H + G::Frames * hop) r <<= 1;
+    return r;
+  }
+  static size_t lds(int hop) {
+    return (size_t)G::Frames * G::FrameLds * sizeof(float2) + (size_t)(ring(hop) + hop) * sizeof(float);
+  }
+};
+
+template <int LOGH>
+__global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_gate_stft(const float* __restrict__ x, int64_t n, int64_t x_stride,
+                                                                      int hop, int s, int rounds, int ring,
+                                                                      const float* __restrict__ window, const float2* __restrict__ tw,
+                                                                      const float2* __restrict__ post, const float* __restrict__ cutoff,
+                                                                      float low, float* __restrict__ y, int64_t y_stride,
+                                                                      int64_t n_frames_i, float fscale, float iscale) {
+  using G = FftGeom<LOGH>;
+  constexpr int H = G::H, T = G::T, n_fft = 2 * H, P = (H / 2) / T;
+  extern __shared__ __attribute__((aligned(16))) float2 lds[];
+  float* acc = reinterpret_cast<float*>(lds + G::Frames * G::FrameLds);
+  float* env_tab = acc + ring;
+  const int tid = threadIdx.x;
+  const int u = tid / T, j = tid - u * T;
+  float2* X = lds + u * G::FrameLds;
+  x += blockIdx.y;                                   // channel
+  y += blockIdx.y;
+  const int64_t N = n + H;                           // fix_length(x, n + n_fft // 2)
+  const int NF = G::Frames * rounds, OUT = NF - (s - 1);
+  const int64_t TT_lo = (int64_t)blockIdx.x * OUT * hop, TT_hi = TT_lo + (int64_t)OUT * hop;   // owned overlap-add range
+  const int64_t st_lo = TT_lo > H ? TT_lo : H, st_hi = TT_hi < N ? TT_hi : N;            // ... that is output: t = TT - H < n
+  const int64_t f_start = (int64_t)blockIdx.x * OUT - (s - 1);
+  const int64_t ola_len = (int64_t)n_fft + (int64_t)hop * (n_frames_i - 1);
+  for (int i = tid; i < ring; i += G::Threads) acc[i] = 0.0f;
+  // window-sum-square by phase where every covering frame exists (frames ascending = offsets descending, as K_istft)
+  for (int ph = tid; ph < hop; ph += G::Threads) {
+    float e = 0.0f;
+    for (int o = ph + ((n_fft - 1 - ph) / hop) * hop; o >= 0; o -= hop) e += window[o] * window[o];
+    env_tab[ph] = e;
+  }
+  // per-lane constants of every frame: window taps of the lane's points, untangle twiddles, the cutoffs of its bins
+  float2 wq[8], pk[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    wq[q] = *reinterpret_cast<const float2*>(window + 2 * (j + q * T));
+    pk[q] = cconj(post[j + q * T]);
+  }
+  float2 pw[P + 1];
+  float ck[P + 1], cm[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    pw[i] = post[j + i * T];
+    ck[i] = cutoff[j + i * T];
+    cm[i] = cutoff[H - j - i * T];
+  }
+  pw[P] = post[H / 2];
+  ck[P] = cutoff[H / 2];
+  const float hs = 0.5f * fscale;
+  // inverse input z[k] = conj(0.5 (ev + i od)) of the gated bins a = X[k], b = X[H - k] (K_istft's operations)
+  auto inv = [&](float2 a, float2 b, float2 cp, bool dc) {
+    if (dc) {
+      a.y = 0.0f;
+      b.y = 0.0f;
+    }
+    b = cconj(b);
+    const float2 ev = cadd(a, b);
+    const float2 od = cmul(cp, csub(a, b));
+    return make_float2(0.5f * (ev.x - od.y), -0.5f * (ev.y + od.x));
+  };
+  __syncthreads();
+  const int64_t interior_lo = n_fft - 1, interior_hi = (int64_t)hop * (n_frames_i - 1);
+  for (int r = 0; r < rounds; ++r) {
+    const int64_t f0 = f_start + (int64_t)r * G::Frames;
+    if (f0 * hop >= st_hi) break;                                   // workgroup-uniform: nothing left to store
+    const int64_t fr = f0 + u;
+    const bool live = fr >= 0 && fr < n_frames_i;
+    // gather + window + pack (K_stft's products: window * sample)
+    float2 v[8];
+    const long long base = (long long)fr * hop - H;
+    if (live && base >= 0 && base + n_fft <= n) {
+      const float* xs = x + base * x_stride;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        v[q] = make_float2(wq[q].x * xs[(int64_t)t0 * x_stride], wq[q].y * xs[(int64_t)(t0 + 1) * x_stride]);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        float2 z = make_float2(0.0f, 0.0f);
+        if (live) {
+          const long long i0 = reflect_index(base + t0, N), i1 = reflect_index(base + t0 + 1, N);
+          z.x = wq[q].x * (i0 < n ? x[i0 * x_stride] : 0.0f);
+          z.y = wq[q].y * (i1 < n ? x[i1 * x_stride] : 0.0f);
+        }
+        v[q] = z;
+      }
+    }
+    fft_core<LOGH>(v, X, j, tw);
+    // untangle (K_stft mode 0: X[k] = (ev - i t) / 2 / sqrt(n_fft)), gate, and the inverse input of the same pair, written
+    // back to the two slots this lane just read (the pair sets of the lanes are disjoint)
+#pragma unroll
+    for (int i = 0; i <= P; ++i) {
+      const int k = (i < P) ? j + i * T : H / 2;
+      if (i == P && j != 0) break;
+      const int sk = lpad(k), sm = lpad((H - k) & (H - 1));
+      const float2 zk = X[sk];
+      const float2 zc = cconj(X[sm]);
+      const float2 ev = cadd(zk, zc);
+      const float2 t = cmul(pw[i], csub(zk, zc));
+      const float2 gk = gate_bin(make_float2((ev.x + t.y) * hs, (ev.y - t.x) * hs), ck[i], low);
+      if (i == P) {                                                  // k = H/2 pairs with itself
+        X[sk] = inv(gk, gk, cconj(post[H / 2]), false);
+      } else {
+        const float2 gm = gate_bin(make_float2((ev.x - t.y) * hs, (-ev.y - t.x) * hs), cm[i], low);   // bin H - k
+        X[sk] = inv(gk, gm, pk[i], k == 0);
+        if (k != 0) X[sm] = inv(gm, gk, cconj(post[H - k]), false);
+      }
+    }
+    frame_sync<T>();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = X[lpad(j + q * T)];
+    fft_core<LOGH>(v, X, j, tw);
+    // windowed time samples, in place: y[2i] = re, y[2i+1] = -im of conj(FFT(conj Z)) (K_istft's scaling)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int i = j + q * T;
+      const float2 z = X[lpad(i)];
+      X[lpad(i)] = make_float2(z.x * iscale * wq[q].x, -z.y * iscale * wq[q].y);
+    }
+    __syncthreads();
+    // overlap-add of the round's frames into the ring, frames ascending
+    const int span = (G::Frames - 1) * hop + n_fft;
+    for (int p = tid; p < span; p += G::Threads) {
+      int u_hi = p / hop;
+      if (u_hi > G::Frames - 1) u_hi = G::Frames - 1;
+      const int u_lo = p - n_fft + 1 <= 0 ? 0 : (p - n_fft + hop) / hop;
+      float* slot = acc + ((f0 * hop + p) & (ring - 1));
+      float a = *slot;
+      for (int w = u_lo; w <= u_hi; ++w) {
+        const int64_t fw = f0 + w;
+        if (fw < 0 || fw >= n_frames_i) continue;
+        const int off = p - w * hop;
+        const float2 pr = lds[w * G::FrameLds + lpad(off >> 1)];
+        a += (off & 1) ? pr.y : pr.x;
+      }
+      *slot = a;
+    }
+    __syncthreads();
+    // the round completes [f0 hop, (f0 + Frames) hop): normalise and store what this run owns, clear the ring slots
+    for (int p = tid; p < G::Frames * hop; p += G::Threads) {
+      const int64_t TT = f0 * hop + p;
+      float* slot = acc + (TT & (ring - 1));
+      float a = *slot;
+      *slot = 0.0f;
+      if (TT < TT_lo || TT < st_lo || TT >= st_hi) continue;
+      if (TT < ola_len) {
+        float env;
+        if (TT >= interior_lo && TT <= interior_hi) {
+          env = env_tab[TT % hop];
+        } else {
+          int64_t e_hi = TT / hop;
+          if (e_hi > n_frames_i - 1) e_hi = n_frames_i - 1;
+          const int64_t e_lo = (TT - n_fft + 1 <= 0) ? 0 : (TT - n_fft + hop) / hop;
+          env = 0.0f;
+          for (int64_t e = e_lo; e <= e_hi; ++e) {
+            const float w = window[TT - e * hop];
+            env += w * w;
+          }
+        }
+        if (env > 1.17549435e-38f) a /= env;                          // > tiny(float32)  (util/fourier.py:414-415)
+      } else {
+        a = 0.0f;
+      }
+      y[(TT - H) * y_stride] = a;
+    }
+  }
+}
+
 }  // namespace par
 
 extern "C" {
@@ -1769,6 +1997,104 @@ extern "C" int par_spec_apply_gain_db_c64(int device, float* spec, const float* 
   PAR_HIP_CHECK(hipSetDevice(device));
   hipLaunchKernelGGL(k_apply_gain_db, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<float2*>(spec), gain_db, count);
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+// ---- renoiser gate entry points (ABI 108) -------------------------------------------------------------------------------------
+extern "C" int par_gate_spectrum_f32(int device, float* spec, int64_t n_frames, int64_t bins, int64_t pitch, const float* cutoff,
+                                     float low, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(spec && cutoff, PAR_ERR_ARG, "par_gate_spectrum_f32: null pointer");
+  const int64_t p = pitch ? pitch : bins;
+  PAR_REQUIRE(n_frames >= 0 && bins >= 1 && p >= bins, PAR_ERR_ARG, "par_gate_spectrum_f32: bad sizes (frames %lld, bins %lld, pitch %lld)",
+              (long long)n_frames, (long long)bins, (long long)pitch);
+  PAR_REQUIRE(ceil_div(bins, 256) <= 0x7fffffff, PAR_ERR_UNSUPPORTED, "par_gate_spectrum_f32: too many bins");
+  if (n_frames == 0) return PAR_OK;
+  PAR_HIP_CHECK(hipSetDevice(device));
+  const int64_t gy = n_frames < 4096 ? n_frames : 4096;
+  hipLaunchKernelGGL(k_gate_spectrum, dim3((unsigned)ceil_div(bins, 256), (unsigned)gy), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<float2*>(spec), n_frames, bins, p, cutoff, low);
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+static int gate_stft_sizes(int64_t n, int n_fft, int hop, int64_t* n_frames_i, int* s, int* rounds, int* ring, int64_t* runs,
+                           size_t* lds) {
+  using namespace par;
+  if (n < 1 || hop < 1 || hop > n_fft || n_fft < 16 || n_fft > 8192 || (n_fft & (n_fft - 1))) return PAR_ERR_UNSUPPORTED;
+  const int64_t frames = par_stft_frames(n + n_fft / 2, n_fft, hop);                    // STFT of fix_length(x, n + n_fft/2)
+  const int64_t want = ceil_div(n + n_fft, hop);                                        // istft(length=n) keeps these
+  *n_frames_i = frames < want ? frames : want;
+  *s = (int)ceil_div(n_fft, hop);
+#define PAR_GATE_GEOM(LH)                                                          \
+  case LH:                                                                         \
+    *rounds = GateGeom<LH>::rounds(*s);                                            \
+    *ring = GateGeom<LH>::ring(hop);                                               \
+    *lds = GateGeom<LH>::lds(hop);                                                 \
+    *runs = ceil_div(n + n_fft / 2, (int64_t)(FftGeom<LH>::Frames * *rounds - (*s - 1)) * hop); \
+    return (*lds <= 160 * 1024) ? PAR_OK : PAR_ERR_UNSUPPORTED;
+  switch (ilog2(n_fft / 2)) {
+    PAR_GATE_GEOM(3) PAR_GATE_GEOM(4) PAR_GATE_GEOM(5) PAR_GATE_GEOM(6) PAR_GATE_GEOM(7)
+    PAR_GATE_GEOM(8) PAR_GATE_GEOM(9) PAR_GATE_GEOM(10) PAR_GATE_GEOM(11) PAR_GATE_GEOM(12)
+  }
+#undef PAR_GATE_GEOM
+  return PAR_ERR_UNSUPPORTED;
+}
+
+extern "C" int64_t par_gate_stft_transformed_frames(int64_t n, int n_fft, int hop) {
+  int64_t nfi = 0, runs = 0;
+  int s = 0, rounds = 0, ring = 0;
+  size_t lds = 0;
+  if (gate_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds) != PAR_OK) return 0;
+  const int frames_per_round = (int)((n_fft / 2) / 8 > 256 ? 1 : 256 / ((n_fft / 2) / 8));
+  // every run but the last transforms all its rounds; the last stops once its rounds reach the end of the output
+  const int64_t out = (int64_t)frames_per_round * rounds - (s - 1);
+  int64_t total = 0;
+  for (int64_t b = 0; b < runs; ++b) {
+    const int64_t f_start = b * out - (s - 1), st_hi = (b + 1) * out * hop < n + n_fft / 2 ? (b + 1) * out * hop : n + n_fft / 2;
+    for (int r = 0; r < rounds; ++r) {
+      if ((f_start + (int64_t)r * frames_per_round) * hop >= st_hi) break;
+      total += frames_per_round;
+    }
+  }
+  return total;
+}
+
+extern "C" int par_gate_stft_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_ch, int n_fft, int hop,
+                                 const float* window, const float* cutoff, float low, float* y, int64_t y_stride, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(x && window && cutoff && y, PAR_ERR_ARG, "par_gate_stft_f32: null pointer");
+  PAR_REQUIRE(n >= 1 && n_ch >= 1 && n_ch <= 65535 && x_stride >= n_ch && y_stride >= n_ch && hop >= 1, PAR_ERR_ARG,
+              "par_gate_stft_f32: bad sizes (n %lld, channels %d, strides %lld / %lld, hop %d)", (long long)n, n_ch,
+              (long long)x_stride, (long long)y_stride, hop);
+  int64_t nfi = 0, runs = 0;
+  int s = 0, rounds = 0, ring = 0;
+  size_t lds = 0;
+  PAR_REQUIRE(gate_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds) == PAR_OK, PAR_ERR_UNSUPPORTED,
+              "par_gate_stft_f32: n_fft=%d hop=%d (a power of two in [16, 8192], 1 <= hop <= n_fft)", n_fft, hop);
+  PAR_REQUIRE(runs <= 0x7fffffff, PAR_ERR_UNSUPPORTED, "par_gate_stft_f32: signal too long");
+  PAR_HIP_CHECK(hipSetDevice(device));
+  Twiddles tw;
+  int rc = get_twiddles(device, n_fft, &tw);
+  if (rc != PAR_OK) return rc;
+  const float fscale = (float)(1.0 / sqrt((double)n_fft));
+  const float iscale = (float)(sqrt((double)n_fft) / (double)(n_fft / 2));
+#define PAR_GATE_LAUNCH(LH)                                                                                              \
+  case LH: {                                                                                                             \
+    rc = raise_dynamic_lds(reinterpret_cast<const void*>(&k_gate_stft<LH>), (int)lds, device);                           \
+    if (rc != PAR_OK) return rc;                                                                                         \
+    hipLaunchKernelGGL(k_gate_stft<LH>, dim3((unsigned)runs, (unsigned)n_ch), dim3(FftGeom<LH>::Threads), lds,           \
+                       as_stream(stream), x, n, x_stride, hop, s, rounds, ring, window, tw.w, tw.post, cutoff, low, y,   \
+                       y_stride, nfi, fscale, iscale);                                                                   \
+    break;                                                                                                               \
+  }
+  switch (ilog2(n_fft / 2)) {
+    PAR_GATE_LAUNCH(3) PAR_GATE_LAUNCH(4) PAR_GATE_LAUNCH(5) PAR_GATE_LAUNCH(6) PAR_GATE_LAUNCH(7)
+    PAR_GATE_LAUNCH(8) PAR_GATE_LAUNCH(9) PAR_GATE_LAUNCH(10) PAR_GATE_LAUNCH(11) PAR_GATE_LAUNCH(12)
+    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_gate_stft_f32: unsupported size");
+  }
+#undef PAR_GATE_LAUNCH
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }

@@ -1,0 +1,242 @@
+"""Headless restatement of the renoiser, the suite's noise-floor tool (reference renoiser_gui.Canvas; experiments/renoiser.py is
+its command-line prototype).
+
+    prof = noise_profile(noise, noise_sr, sr)                     # load_noise_profile (renoiser_gui.py:239-250)
+    prof = noise_profile_from_selection(signal, sr, t0, t1)       # on_mouse_release (:327-345)
+    final = final_profile(prof, sr, 2048)                         # redraw_plot (:280-294)
+    out = renoise(signal, sr, final)                              # get_mask_fac + run_resample (:273-278, :296-319)
+    renoise_file("tape.wav", noise_path="hiss.wav")               # ... written as "tape fft=2048.wav"
+
+Per selected channel the reference zero-extends the signal by n_fft/2, takes a complex STFT (blackmanharris, zero padding 1),
+multiplies a binary per-bin gain mask in (a bin whose float32 dB is above the final profile passes, every other bin gets `gain`
+dB) and runs the ISTFT.  Here that whole chain is one launch of par_gate_stft_f32 for all channels (n_fft <= 8192: no
+spectrogram reaches HBM); larger transforms compose K_stft, par_gate_spectrum_f32 and K_istft.  The mask's float32 decibels
+become one float32 magnitude cutoff per bin on the host (gate_cutoffs), so the kernels decide exactly as numpy does on the
+same spectrum.
+
+Differences from the reference:
+- Noise at another sample rate raises ValueError.  The GUI first passes it through resampy's sinc_window resampler
+  (num_zeros=8); the profile is taken from the samples as given when the rates are equal, which is also what
+  experiments/renoiser.py does then.
+- An empty selection (no frame between t0 and t1) raises ValueError; the reference would produce a NaN profile.
+- The input is never modified.  Repeated channel numbers raise ValueError (the reference leaves the columns they skip
+  uninitialised); a channel number at or above the number of selected channels raises IndexError, as the reference's
+  y_out[:, channel_i] does.
+- Both profiles are float64 sums over frames of the float32 magnitudes K_stft computes (decibels for a noise file); the
+  reference's numpy backend averages float64 values of its own STFT.  NOTES.md gives the bound.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import _dev, _lib, fourier, io_ops, spectrum_flat
+
+WINDOW = "blackmanharris"
+# GUI defaults (util/widgets.py:768-810, 326-351): FFT 2048, overlap 4, gain 12 dB, overhead 3 dB, zero padding forced to 1
+FFT_SIZE, OVERLAP, GAIN, OVERHEAD = 2048, 4, 12.0, 3.0
+NO_PROFILE_DB = -100.0
+
+
+def _as_2d(signal):
+    return signal if signal.ndim == 2 else signal[:, None]
+
+
+def _db32(mag):
+    """util/units.to_dB on float32 magnitudes: float32 20 * log10(m)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.float32(20) * np.log10(np.asarray(mag, dtype=np.float32))
+
+
+def default_profile(sr, fft_size=FFT_SIZE):
+    """The profile before any noise is loaded: -100 dB in every bin (renoiser_gui.py:204-205)."""
+    return np.full(len(fourier.fft_freqs(fft_size, sr)), NO_PROFILE_DB, dtype=np.float32)
+
+
+def noise_profile(noise, noise_sr, sr, fft_size=FFT_SIZE, hop=FFT_SIZE // OVERLAP, device=None):
+    """Mean decibel spectrum of the first channel of a noise recording, float64 (bins,) like the reference's numpy STFT backend
+    makes it -- load_noise_profile.  The noise must be at the signal's rate (ValueError otherwise: there is no resampy pass)."""
+    if int(noise_sr) != int(sr):
+        raise ValueError(f"noise sample rate {noise_sr} != signal rate {sr}: resample the noise first (no resampy pass here)")
+    dev = _dev.device_index(device if device is not None else (noise.device if torch.is_tensor(noise) else None))
+    n2d = _as_2d(noise)
+    n, ch = n2d.shape
+    flat = _dev.to_dev(n2d, torch.float32, dev).reshape(-1)
+    mean = spectrum_flat.mean_spectrum_db_dev(flat, fft_size, hop, WINDOW, 1, x_stride=ch, n=n, dev=dev)
+    return _dev.to_host(mean)
+
+
+def selection_frames(t0, t1, sr, hop, n_frames):
+    """Frame range [f0, f1) of a selection from t0 to t1 seconds (renoiser_gui.py:336-341)."""
+    f0 = max(0, int(t0 * sr / hop))
+    f1 = min(int(t1 * sr / hop), n_frames - 1)
+    return f0, f1
+
+
+def noise_profile_from_selection(signal, sr, t0, t1, fft_size=FFT_SIZE, hop=FFT_SIZE // OVERLAP, channel=0, device=None):
+    """to_dB of the mean magnitude spectrum (|X| + 1e-7) of frames [f0, f1) of one channel, float64 (bins,) --
+    on_mouse_release.  ValueError when the range holds no frame."""
+    s2d = _as_2d(signal)
+    n, ch = s2d.shape
+    if not 0 <= channel < ch:
+        raise IndexError(f"channel {channel} of a {ch}-channel signal")
+    frames = int(_lib.lib().par_stft_frames(n, fft_size, hop))
+    f0, f1 = selection_frames(t0, t1, sr, hop, frames)
+    if f1 <= f0:
+        raise ValueError(f"the selection {t0}-{t1} s holds no frame (frames {f0}..{f1}): the reference would make a NaN profile")
+    dev = _dev.device_index(device if device is not None else (signal.device if torch.is_tensor(signal) else None))
+    flat = _dev.to_dev(s2d, torch.float32, dev).reshape(-1)
+    window_t = fourier.window_dev(WINDOW, fft_size, dev)
+    bins = fft_size // 2 + 1
+    acc = torch.zeros(bins, dtype=torch.float64, device=f"cuda:{dev}")
+    L = _lib.lib()
+    for c0, c1, fm in spectrum_flat.mag_chunks_dev(flat[channel:], fft_size, hop, window_t, 1, ch, n, dev):
+        a, b = max(c0, f0), min(c1, f1)
+        if a < b:
+            rows = fm[a - c0:b - c0]
+            _lib.check(L.par_mean_mag_frames_f32(dev, _dev.ptr(rows), b - a, bins, rows.stride(0), _dev.ptr(acc), _dev.stream_ptr(dev)))
+    return 20 * np.log10(_dev.to_host(acc) / (f1 - f0))
+
+
+def final_profile(noise_profile, sr, fft_size=FFT_SIZE, gain=GAIN, overhead=OVERHEAD, curve=None):
+    """noise profile + gain + the control curve interpolated at the bin frequencies + overhead, float64 (bins,) -- redraw_plot.
+    curve: [[Hz, dB], ...] (default [[1, 0], [sr/2, 0]]), sorted like the GUI's list.  The profile keeps its dtype: for a
+    float32 profile the gain is added in float32 first, exactly as numpy does there."""
+    freqs = fourier.fft_freqs(fft_size, sr)
+    pts = sorted([list(p) for p in ([[1, 0], [sr / 2, 0]] if curve is None else curve)])
+    cx, cy = zip(*pts)
+    prof = np.asarray(noise_profile)
+    if prof.dtype not in (np.float32, np.float64):
+        prof = prof.astype(np.float64)
+    if prof.shape != freqs.shape:
+        raise ValueError(f"noise profile has {prof.shape} bins, the FFT size {fft_size} has {freqs.shape}")
+    return prof + float(gain) + np.interp(freqs, cx, cy) + float(overhead)
+
+
+def gate_cutoffs(final):
+    """float32 magnitude cutoffs of a float64 threshold profile: for every float32 magnitude m >= 0,
+    float32(20 log10(m)) > final[k]  <=>  m >= cutoff[k]  (numpy's float32 log10 is monotone).  Found by bisection over the
+    float32 bit patterns with numpy's own float32 decibels; a threshold no magnitude exceeds (NaN, +inf) gives a NaN cutoff,
+    which gates every magnitude, NaN included."""
+    thr = np.asarray(final, dtype=np.float64)
+
+    def above(bits):
+        return _db32(bits.view(np.float32)) > thr
+    lo = np.zeros(thr.shape, dtype=np.uint32)                       # 0.0: -inf dB, above no threshold
+    hi = np.full(thr.shape, 0x7F800000, dtype=np.uint32)            # +inf
+    ok = above(hi.copy())
+    while True:
+        gap = hi - lo
+        if not np.any(gap > 1):
+            break
+        mid = lo + gap // 2
+        m_above = above(mid)
+        hi = np.where(m_above, mid, hi)
+        lo = np.where(m_above, lo, mid)
+    cut = hi.view(np.float32).copy()
+    cut[~ok] = np.nan
+    return cut
+
+
+def low_factor(gain):
+    """The mask's factor for gated bins: float32(10^(gain/20)) (util/units.to_fac in float64, then float32)."""
+    return np.float32(np.power(10, float(gain) / 20))
+
+
+def fused_supported(fft_size, hop):
+    """par_gate_stft_f32 takes power-of-two transforms of 16..8192 points with 1 <= hop <= n_fft."""
+    return 16 <= fft_size <= 8192 and (fft_size & (fft_size - 1)) == 0 and 1 <= hop <= fft_size
+
+
+def _check_channels(channels, ch):
+    chans = [int(c) for c in channels]
+    if len(set(chans)) != len(chans):
+        raise ValueError(f"channels {chans} repeat a channel")
+    for c in chans:
+        if c >= len(chans) or c >= ch or c < 0:
+            raise IndexError(f"index {c} is out of bounds for axis 1 with size {min(len(chans), ch)}")
+    return chans
+
+
+def renoise_dev(sig_t, final, gain=GAIN, fft_size=FFT_SIZE, hop=FFT_SIZE // OVERLAP, channels=None, dev=None, fused=None, out=None):
+    """Device form of renoise: sig_t float32 (n, ch) device tensor -> float32 (n, len(channels)) device tensor.  fused: None
+    picks by size (par_gate_stft_f32 up to 8192 points), False forces the composed path (K_stft -> par_gate_spectrum_f32 ->
+    K_istft per channel; the tests' reference for the fused kernel)."""
+    dev = _dev.device_index(dev if dev is not None else sig_t.device)
+    L = _lib.lib()
+    n, ch = sig_t.shape
+    chans = _check_channels(range(ch) if channels is None else channels, ch)
+    k = len(chans)
+    if k == 0:
+        raise ValueError("no channel selected")
+    bins = fft_size // 2 + 1
+    thr = np.asarray(final, dtype=np.float64)
+    if thr.shape != (bins,):
+        raise ValueError(f"final profile has {thr.shape} bins, the FFT size {fft_size} has {bins}")
+    cut_t = _dev.to_dev(gate_cutoffs(thr), torch.float32, dev)
+    low = float(low_factor(gain))
+    window_t = fourier.window_dev(WINDOW, fft_size, dev)
+    if out is None:
+        out = _dev.empty((n, k), torch.float32, dev)
+    use_fused = fused_supported(fft_size, hop) if fused is None else fused
+    stream = _dev.stream_ptr(dev)
+    if use_fused:
+        # channels are a permutation of 0..k-1 (checked above): channel c -> column c, all in one launch
+        _lib.check(L.par_gate_stft_f32(dev, _dev.ptr(sig_t), n, ch, k, fft_size, hop, _dev.ptr(window_t), _dev.ptr(cut_t), low,
+                                       _dev.ptr(out), out.stride(0), stream))
+        return out
+    half = fft_size // 2
+    for c in chans:
+        xpad = torch.zeros(n + half, dtype=torch.float32, device=f"cuda:{dev}")        # fourier.fix_length(sig, n + n_fft // 2)
+        xpad[:n] = sig_t[:, c]
+        spec = fourier.stft_dev(xpad, fft_size, hop, window_t, 1, 0, dev=dev)         # (bins, frames) view of [frames][bins]
+        fm = spec.T
+        _lib.check(L.par_gate_spectrum_f32(dev, _dev.ptr(fm), fm.shape[0], bins, 0, _dev.ptr(cut_t), low, stream))
+        out[:, c] = fourier.istft_dev(spec, hop, window_t, length=n, dev=dev)
+    return out
+
+
+def renoise(signal, sr, final, gain=GAIN, fft_size=FFT_SIZE, hop=FFT_SIZE // OVERLAP, channels=None, device=None):
+    """run_resample of the GUI on an (n, ch) (or (n,)) float32 signal: returns float32 (n, len(channels)) -- numpy for numpy
+    input, a device tensor for a tensor; a 1-D input gives a 1-D result.  channels: the selected channel numbers (default
+    all).  `final` is the float64 threshold profile (final_profile), `gain` the dB every bin at or under it gets."""
+    dev = _dev.device_index(device if device is not None else (signal.device if torch.is_tensor(signal) else None))
+    was_tensor = torch.is_tensor(signal)
+    sig2d = _as_2d(signal)
+    sig_t = _dev.to_dev(sig2d, torch.float32, dev).contiguous()
+    out = renoise_dev(sig_t, final, gain, fft_size, hop, channels, dev)
+    res = out if signal.ndim == 2 else out[:, 0]
+    return res if was_tensor else _dev.to_host(res)
+
+
+def output_path(path, fft_size):
+    """The file run_resample writes: io_ops.write_file(path, ..., suffix=f" fft={fft_size}")"""
+    return f"{os.path.splitext(path)[0]} fft={fft_size}.wav"
+
+
+def renoise_file(path, noise_path=None, selection=None, fft_size=FFT_SIZE, overlap=OVERLAP, gain=GAIN, overhead=OVERHEAD,
+                 curve=None, channels=None, device=None, signal_data=None):
+    """The GUI's flow on a file: read `path` (signal_data=(signal, sr, channels) skips the read); the noise profile comes from
+    the noise file `noise_path` (same rate), from the time range selection=(t0, t1) of channel 0, or is the -100 dB default;
+    apply and write "<stem> fft=<N>.wav" (float32 WAV).  Returns the written path, or None when no channel is selected (the
+    reference then writes nothing)."""
+    if noise_path is not None and selection is not None:
+        raise ValueError("give a noise file or a selection, not both")
+    dev = _dev.device_index(device)
+    signal, sr, num_channels = io_ops.read_file(path) if signal_data is None else signal_data
+    hop = fft_size // overlap
+    chans = list(range(_as_2d(signal).shape[1])) if channels is None else list(channels)
+    if not chans:
+        return None
+    sig_t = _dev.to_dev(_as_2d(signal), torch.float32, dev).contiguous()
+    if noise_path is not None:
+        noise, noise_sr, _ = io_ops.read_file(noise_path)
+        prof = noise_profile(noise, noise_sr, sr, fft_size, hop, dev)
+    elif selection is not None:
+        prof = noise_profile_from_selection(sig_t, sr, selection[0], selection[1], fft_size, hop, 0, dev)
+    else:
+        prof = default_profile(sr, fft_size)
+    final = final_profile(prof, sr, fft_size, gain, overhead, curve)
+    out = _dev.to_host(renoise_dev(sig_t, final, gain, fft_size, hop, chans, dev))
+    io_ops.write_file(path, out, sr, len(chans), suffix=f" fft={fft_size}")
+    return output_path(path, fft_size)
