@@ -38,7 +38,11 @@
 #include "pos_plan.h"
 #include "sinc_taps_gen.h"
 #include "sinc_common.h"
+#define PAR_COLD_FN __forceinline__      // (the end tiles' float64 cold functions inline: no private segment for the streaming kernels)
 #include "sinc_block.h"           // fused_wave: the file's end tiles are done the block kernel's way by the launch's first workgroups
+#ifndef PAR_COLD_FN_GIVEN
+#error "sinc_block.h was included before PAR_COLD_FN was defined: the cold functions would stay out of line"
+#endif
 #include <algorithm>
 #include <atomic>
 #include <limits.h>
@@ -224,6 +228,22 @@ __device__ __forceinline__ S2Row s2_place_row(const uint4 ra, const uint4 rb, co
 // s_waitcnt vmcnt(5) (everything but the previous iteration's five memory operations has landed), no branch in the body.
 // The ring holds 8 chunks of float32 samples (near taps) and 4 of the float16 images; the bank is single-buffered (an
 // iteration's gathers precede its bank writes in program order, LDS serves a wave's operations in order).
+// Order of one iteration of the MONO loop at two waves per SIMD, as built with -DPAR_S3_EARLY_LDS=1 (k_sinc_pipe<1, 2>; the default, 0,
+// is the r06 order above: the new one becomes the default once its A/B against it is on record, NOTES).
+// At four waves a wave that waits for its own LDS read is covered by the other three; at two it is not, so every read is
+// issued a stage ahead of its use:
+//     wait vmcnt + fence
+//     READS    the records of PLACE(k + 1), CONV's ring chunk, the gathers of OUT(k) (3 rows + 5 ring samples per output):
+//              their addresses are loop state, the data landed before the fence
+//     PLACE(k + 1) behind a partial lgkmcnt (the records alone); the loop's exit test (scalar) rides beside it
+//     READS    BANK(k + 1)'s six image fragments, as soon as ws is known
+//     OUT(k)   arithmetic, pinned here: the fragments land under it
+//     BANK(k + 1) MFMAs, row writes (behind OUT(k)'s gathers); CONV arithmetic + image writes (behind the fragment reads)
+//     FETCH, DMA, stores, fence
+// Same hazards as above -- nothing read that the iteration wrote, gathers before row writes, fragment reads before image writes,
+// one fence, one vmcnt wait -- and the same arithmetic expressions.  (Whether the outputs are bit-identical to the r06 order's --
+// the compiler contracts multiplies and adds across statements, and the block structure moved -- is for a dump comparison to show.)
+// (tools/isa_census.py --waits lists each read, the wait that covers it and the wave's own vector work in between.)
 // Whatever is not the plain case -- the first pass of a run, a pass that meets a flagged tile or block, the end of the
 // wave's range, a change of tap regime, a conversion window that has drifted out of its slack -- leaves the loop
 // and is done by start_run(): the same stages, one after the other with full waits, which also primes the loop again.
@@ -275,18 +295,28 @@ struct S3Pass {                                  // a placed pass: 128 candidate
 // (kBank3Frags32, sinc_taps_gen.h); all resident in the wave's registers.  MOMENTS = false: the fc = 1 bank alone.
 constexpr int kCtabUnity = 10;
 // SIX = false: without the moment of order 6 (passes with 1 - fc <= 0.0105: the series to order 5 is within 1.6e-6 there)
-template <bool MOMENTS, bool SIX = true, class LDS>
-__device__ __forceinline__ void bank_image3m(LDS& L, const half8v (&fr)[kBank2Frags], const half8v (&fmr)[kBank3Frags],
-                                             const int offs, const int l, const int ch = 0) {
+// (in two halves: the six signal fragments read from the images, and the matrix work with the row writes)
+struct S3Frags {
+  half8v xh[3], xl[3];
+};
+template <class LDS>
+__device__ __forceinline__ S3Frags bank_load(const LDS& L, const int offs, const int l, const int ch = 0) {
   const int bb = l & 15, g = l >> 4;
   const int i0 = offs + 8 * bb + 8 * g;
-  half8v xh[3], xl[3];
+  S3Frags X;
 #pragma unroll
   for (int ks = 0; ks < 3; ++ks) {
     const int ix = (i0 + 32 * ks) & (kRingH - 1);
-    xh[ks] = *reinterpret_cast<const half8v*>(&L.img[2 * ch][ix]);
-    xl[ks] = *reinterpret_cast<const half8v*>(&L.img[2 * ch + 1][ix]);
+    X.xh[ks] = *reinterpret_cast<const half8v*>(&L.img[2 * ch][ix]);
+    X.xl[ks] = *reinterpret_cast<const half8v*>(&L.img[2 * ch + 1][ix]);
   }
+  return X;
+}
+template <bool MOMENTS, bool SIX = true, class LDS>
+__device__ __forceinline__ void bank_math(LDS& L, const half8v (&fr)[kBank2Frags], const half8v (&fmr)[kBank3Frags],
+                                          const S3Frags& X, const int l) {
+  const int bb = l & 15, g = l >> 4;
+  const half8v (&xh)[3] = X.xh, (&xl)[3] = X.xl;
   auto frag = [&](int f) { return f < kCtabUnity ? fr[f] : fmr[f - kCtabUnity]; };
   const float4v z = {0.0f, 0.0f, 0.0f, 0.0f};
   float4v e0 = z, lo = z, e1 = z, e2 = z;
@@ -336,32 +366,52 @@ __device__ __forceinline__ void bank_image3m(LDS& L, const half8v (&fr)[kBank2Fr
     }
   }
 }
+template <bool MOMENTS, bool SIX = true, class LDS>
+__device__ __forceinline__ void bank_image3m(LDS& L, const half8v (&fr)[kBank2Frags], const half8v (&fmr)[kBank3Frags],
+                                             const int offs, const int l, const int ch = 0) {
+  bank_math<MOMENTS, SIX>(L, fr, fmr, bank_load(L, offs, l, ch), l);
+}
 
 // the outputs of one row of a placed pass (bank and ring in LDS): MODE 1 fc = 1, MODE 3 fc = 1 + the
 // moment correction  -g (cos(pi s) Re Q - sin(pi s) Im Q),  Q = sum_i M_i (i 32 G)^i (alpha_i + i beta_i),  G = pi g, w = G s,
 // alpha_i = 1/(i! (i+1)) - w^2 / (2 i! (i+3)),  beta_i = -w / (i! (i+2))   (tools/sinc3_model.py: 1e-7 for g <= 0.0101)
+// (in two halves: the LDS reads of a row -- its bank and moment rows, the five ring samples of the near taps -- and the
+// arithmetic on them; the mono loop issues the reads at the head of an iteration and works them out a stage later)
+struct S3Gather {
+  float4v row, M0, Mh;                           // {e0, d0, e1, d1}, {m0, m1, m2, e2|d2}, {m3 .. m6}  (MODE 1: M0[3] alone)
+  float xm2, xm1, x0, xp1, xp2;
+};
 template <int MODE, int NCH = 1, class LDS>
-__device__ __forceinline__ float s3_out_row(const LDS& L, const int ci, const float sr, const float epr, const int wsK, const int ch = 0) {
-  using T32 = TapTab<32>;
-  constexpr float kUs = kBank2ScaleInv * kImgScaleInv;      // bank rows -> signal units
-  constexpr float kMs = kImgScaleInv;                       // moment rows -> signal units (rides in the Horner's constants)
+__device__ __forceinline__ S3Gather s3_out_load(const LDS& L, const int ci, const int wsK, const int ch = 0) {
   const int sl = ci ^ ((ci >> 3) & 7);
   const int rc = (wsK + ci) & (kRingF - 1);
   const float* xp = &L.ring[NCH * rc + ch];
-  const float xm2 = xp[-2 * NCH], xm1 = xp[-NCH], x0 = xp[0], xp1 = xp[NCH], xp2 = xp[2 * NCH];
+  S3Gather G;
+  G.xm2 = xp[-2 * NCH], G.xm1 = xp[-NCH], G.x0 = xp[0], G.xp1 = xp[NCH], G.xp2 = xp[2 * NCH];
+  G.row = L.qa[sl];
+  G.M0 = float4v{0.0f, 0.0f, 0.0f, 0.0f};
+  G.Mh = G.M0;
+  if constexpr (MODE != 1) {
+    G.M0 = L.qm0[sl];
+    G.Mh = L.qm1[sl];
+  } else {
+    G.M0[3] = L.e2d2(sl);
+  }
+  return G;
+}
+template <int MODE>
+__device__ __forceinline__ float s3_out_math(const S3Gather& Gr, const float sr, const float epr) {
+  using T32 = TapTab<32>;
+  constexpr float kUs = kBank2ScaleInv * kImgScaleInv;      // bank rows -> signal units
+  constexpr float kMs = kImgScaleInv;                       // moment rows -> signal units (rides in the Horner's constants)
+  const float xm2 = Gr.xm2, xm1 = Gr.xm1, x0 = Gr.x0, xp1 = Gr.xp1, xp2 = Gr.xp2;
   const float q = sr * sr, q64 = 64.0f * q;
   const float R1 = fast_rcp(fmaf(q, T32::B[1], T32::A[1])), R2 = fast_rcp(fmaf(q, T32::B[2], T32::A[2]));
   {
     const float E1 = xp1 + xm1, D1 = xp1 - xm1, E2 = xp2 + xm2, D2 = xp2 - xm2;
-    const float4v row = L.qa[sl];
-    float4v M0 = {0.0f, 0.0f, 0.0f, 0.0f};
-    unsigned w2;
-    if constexpr (MODE != 1) {
-      M0 = L.qm0[sl];
-      w2 = __float_as_uint(M0[3]);
-    } else {
-      w2 = __float_as_uint(L.e2d2(sl));
-    }
+    const float4v row = Gr.row;
+    const float4v M0 = Gr.M0;
+    const unsigned w2 = __float_as_uint(M0[3]);
     const float e = fmaf(q, fmaf(q64, h_lo(w2), row[2]), row[0]), d = fmaf(q, fmaf(q64, h_hi(w2), row[3]), row[1]);
     const float en = fmaf(E2, R2, -(E1 * R1));
     const float dn = fmaf(D2 + D2, R2, -(D1 * R1));
@@ -370,7 +420,7 @@ __device__ __forceinline__ float s3_out_row(const LDS& L, const int ci, const fl
     const float unity = spq * fmaf(-sr, fmaf(sr, et, dt), x0 * 0.318309886f);
     if constexpr (MODE == 1) return unity;
     else {
-    const float4v Mh = L.qm1[sl];
+    const float4v Mh = Gr.Mh;
     const float m3 = Mh[0], m4 = Mh[1], m5 = Mh[2], m6 = Mh[3];
     const float g = epr * fast_rcp(1.0f + epr);                        // 1 - fc
     const float G = 3.14159265f * g, w = G * sr, w2m = w * w, G32 = 32.0f * G;
@@ -402,13 +452,22 @@ __device__ __forceinline__ float s3_out_row(const LDS& L, const int ci, const fl
     }
   }
 }
+template <int MODE, int NCH = 1, class LDS>
+__device__ __forceinline__ float s3_out_row(const LDS& L, const int ci, const float sr, const float epr, const int wsK, const int ch = 0) {
+  return s3_out_math<MODE>(s3_out_load<MODE, NCH>(L, ci, wsK, ch), sr, epr);
+}
 
 // one chunk of the ring -> float16 images (and the ring's mirrors); returns false when float16 does not suit the chunk
+// (in two halves like a row's gather: the lane's two ring samples, and the arithmetic with the image writes)
 template <class LDS>
-__device__ __forceinline__ bool s3_convert(LDS& L, const int chunk, const int l) {
+__device__ __forceinline__ float2 s3_convert_load(const LDS& L, const int chunk, const int l) {
+  const int ix = (chunk * kPass + 2 * l) & (kRingF - 1);
+  return *reinterpret_cast<const float2*>(&L.ring[ix]);
+}
+template <class LDS>
+__device__ __forceinline__ bool s3_convert_math(LDS& L, const int chunk, const int l, const float2 xx) {
   const int wi = chunk * kPass + 2 * l;
   const int ix = wi & (kRingF - 1), ih = wi & (kRingH - 1);
-  const float2 xx = *reinterpret_cast<const float2*>(&L.ring[ix]);
   const float x0 = xx.x, x1 = xx.y;
   const float am = fmaxf(fabsf(x0), fabsf(x1));
   const bool ok = !(__ballot(!(fabsf(x0) < kImgMax) || !(fabsf(x1) < kImgMax)) != 0ull ||       // (also false for NaN)
@@ -421,6 +480,10 @@ __device__ __forceinline__ bool s3_convert(LDS& L, const int chunk, const int l)
   *reinterpret_cast<half2v*>(&L.img[0][ih]) = h;
   *reinterpret_cast<half2v*>(&L.img[1][ih]) = lo;
   return ok;
+}
+template <class LDS>
+__device__ __forceinline__ bool s3_convert(LDS& L, const int chunk, const int l) {
+  return s3_convert_math(L, chunk, l, s3_convert_load(L, chunk, l));
 }
 
 // Stereo ring (frames left, right): channel `ch` of one chunk -> that channel's float16 images.  `mirrors`: the call also keeps the
@@ -461,6 +524,9 @@ constexpr float kEpMom5 = 0.0105f / (1.0f - 0.0105f), kEpMom5Lo = 0.95f * kEpMom
 #ifndef PAR_S3_PIN_MONO
 #define PAR_S3_PIN_MONO 0       // 1: the mono loop's row results pinned like the stereo loop's (234 instead of 250 registers, 1 % slower)
 #endif
+#ifndef PAR_S3_EARLY_LDS
+#define PAR_S3_EARLY_LDS 0      // the mono loop's LDS reads issued a stage ahead of their use (see the loop): 0 = the r06 order, 1 = the
+#endif                          // fc < 1 kernel <1, 2>, 3 = the fc = 1 kernel <1, 1> as well.  0 until the A/B on the GPU is on record (NOTES)
 // KIND: which streams of the launch the kernel takes, and what it has to know for them (r06).  A wave issues an instruction
 // every ~5 cycles whatever its kind, so two waves per SIMD -- what the 25 constant fragments of both filter sets leave room
 // for -- cannot fill the SIMD's issue slots; a stream whose tiles hold fc = 1 outputs only needs the fc = 1 bank's ten:
@@ -483,6 +549,8 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
   constexpr bool kPick = KIND == 3;               // one channel of two-channel frames: stereo ring, mono loop
   constexpr bool kTwo = NCH == 2 && !kPick;       // both channels of a pass: the stereo loop
   constexpr bool kMom = KIND != 1;
+  // the mono loop with its LDS reads a stage ahead (PAR_S3_EARLY_LDS)
+  constexpr bool kEarly = NCH == 1 && ((KIND == 2 && (PAR_S3_EARLY_LDS & 1)) || (KIND == 1 && (PAR_S3_EARLY_LDS & 2) == 2));
   const int l = threadIdx.x & (kWave - 1);
   if (bx < a.n_edge) {                            // an end tile's wave: tile 0, then n_full - 2, n_full - 1 and the partial one
     if constexpr (KIND == 1) return;              // (done by the launch of the other kind)
@@ -608,7 +676,18 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     int epm;                                     // the larger period - 1 of the lane's two outputs, as its bit pattern (ep >= 0: ordered like the floats)
   };
   int tc_T = -1, tc_dA0 = 0, tc_dA1 = 0, tc_fl0 = 0, tc_fl1 = 0;      // anchors and flags of the tile of j and of the one behind it (refreshed once per tile)
-  auto place = [&](int j, int buf, int rb) {
+  struct PlaceRecs {
+    uint4 ra0, rb0, ra1, rb1;                    // first / second pieces of the blocks of the lane's two outputs
+  };
+  auto place_load = [&](int j, int buf, int rb) {
+    const int t5 = (j & (kRec - 1)) + l;
+    const int bi = ((j >> kRecShift) - rb + (t5 >> kRecShift)) & 7;
+    const uint4* rp = &L.recs[buf][0];
+    return PlaceRecs{rp[bi], rp[8 + bi], rp[(bi + 2) & 7], rp[8 + ((bi + 2) & 7)]};
+  };
+  // (EARLY: the records were read ahead by place_load; otherwise they are read here, where the compiler keeps the second pieces'
+  // reads inside the variant that selects them)
+  auto place_impl = [&](int j, int buf, int rb, auto early, const PlaceRecs& RR) {
     Placed P;
     const int T = j >> 10;
     P.tend = (T + 1) << 10;
@@ -624,9 +703,14 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     P.fl1 = tc_fl1;
     const int t5 = (j & (kRec - 1)) + l;
     const int u = t5 & (kRec - 1);
-    const int bi = ((j >> kRecShift) - rb + (t5 >> kRecShift)) & 7;
-    const uint4* rp = &L.recs[buf][0];
-    const uint4 ra0 = rp[bi], rb0 = rp[8 + bi], ra1 = rp[(bi + 2) & 7], rb1 = rp[8 + ((bi + 2) & 7)];
+    uint4 ra0, rb0, ra1, rb1;
+    if constexpr (decltype(early)::value) {
+      ra0 = RR.ra0, rb0 = RR.rb0, ra1 = RR.ra1, rb1 = RR.rb1;
+    } else {
+      const int bi = ((j >> kRecShift) - rb + (t5 >> kRecShift)) & 7;
+      const uint4* rp = &L.recs[buf][0];
+      ra0 = rp[bi], rb0 = rp[8 + bi], ra1 = rp[(bi + 2) & 7], rb1 = rp[8 + ((bi + 2) & 7)];
+    }
     const int uc = u - kRec / 2;
     const float uf = (float)uc, u2f = uf * uf, tw1 = fmaf(2.0f, uf, 1.0f), tw0 = tw1 - 2.0f;
     P.nt[0] = clamp64(P.tend - j);
@@ -644,6 +728,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     P.epm = max(__float_as_int(P.R[0].ep), __float_as_int(P.R[1].ep));
     return P;
   };
+  auto place = [&](int j, int buf, int rb) { return place_impl(j, buf, rb, std::false_type{}, PlaceRecs{}); };
 
   S3Pass P;                                      // the pass OUT works on next (placed, its bank in LDS)
   P.nok[0] = P.nok[1] = 0;
@@ -874,8 +959,8 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       S3Pass N;
       bool ok;
       int wsK;
-      auto place_next = [&]() {
-      const Placed Q = place(j0, pk & 3, rbA);
+      auto place_next = [&](auto early, const PlaceRecs& RR) {
+      const Placed Q = place_impl(j0, pk & 3, rbA, early, RR);
       const unsigned long long bad = __ballot(Q.R[0].bad || Q.R[1].bad || Q.epm > __float_as_int(kEpMaxMom));
       // some lane with fc < 1: 1 + ep != 1 in float32, i.e. ep > 2^-24 (ep >= 0)
       const unsigned long long gen = __ballot(Q.epm > 0x33800000);          // 2^-24
@@ -900,12 +985,53 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
            (MODE == 1 ? gen == 0ull : gen != 0ull) & tier & ((unsigned)(d - 161) <= 312u) & (conv_next + 1 < dma_bad) &
            ((unsigned)((j0 >> kRecShift) - rbA) <= 1u);
       };
-      if constexpr (!kTwo) place_next();          // (stereo: behind OUT(P, 1), fewer registers live through the banks)
+      float res[2];
+      bool cok;
+      if constexpr (kEarly) {
+        // The mono loop, every LDS read issued a stage ahead of its use (the order at the head of this kernel).  The reads whose
+        // addresses the loop's state names: the records of PLACE(pk), the conversion's chunk, the gathers of OUT(P)
+        const PlaceRecs RR = place_load(j0, pk & 3, rbA);
+        const float2 cxx = s3_convert_load(L, conv_next, l);
+        S3Gather G[2];
+        const int wsP = P.ws - wbase;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          int ci = P.c[r] - P.ws;
+          ci = ci < 0 ? 0 : (ci > kPass - 1 ? kPass - 1 : ci);
+          G[r] = s3_out_load<MODE, NCH>(L, ci, wsP);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // PLACE(pk) waits for the records alone; the chunk and the gathers land under it
+        place_next(std::true_type{}, RR);
+        // BANK(pk)'s image fragments set out as soon as ws is known ...
+        const S3Frags X = bank_load(L, wsK - 31, l);
+        __builtin_amdgcn_sched_barrier(0);
+        // ... and OUT(P)'s arithmetic runs while they are on their way.  (Pinned: left alone the compiler sinks a row's arithmetic
+        // into its store's lane mask at the END of the iteration, as in the stereo loop.)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) res[r] = s3_out_math<MODE>(G[r], P.s[r], P.ep[r]);
+        asm volatile("" : "+v"(res[0]), "+v"(res[1]));
+        // (order 5 leaves m6 of the gathered rows unread: kept alive to here, or its register is handed out again under
+        // PLACE and the write to it waits for the LAST gather)
+        if constexpr (MODE == 2) asm volatile("" ::"v"(G[0].Mh[3]), "v"(G[1].Mh[3]));
+        __builtin_amdgcn_sched_barrier(0);
+        // the matrix work and the row writes (behind OUT(P)'s gathers), CONV's arithmetic and image writes (behind the fragment
+        // reads), then FETCH and the stores: five memory operations, in this order
+        bank_math<MODE != 1, MODE == 3>(L, fr, fmr, X, l);
+        // (the loop's exit test is ~35 scalar instructions; left alone they all sink behind the stores, where the wave offers
+        // the vector port nothing: worked out here, beside the matrix work)
+        int oki = __builtin_amdgcn_readfirstlane((int)ok);
+        asm volatile("" : "+s"(oki));
+        ok = oki != 0;
+        cok = s3_convert_math(L, conv_next, l, cxx);
+        fetch_records((pk + 2) & 3, rbC);
+        chunk_dma(dma_next);
+        store_pass(P, res);
+      } else {
+      if constexpr (!kTwo) place_next(std::false_type{}, PlaceRecs{});      // (stereo: behind OUT(P, 1), fewer registers live through the banks)
       // BANK(pk) over [ws, ws + 128): image samples converted in earlier iterations
       // OUT(P) first in program order: its gathers must precede the bank's row writes
-      float res[2];
       out_pass(mode_tag, P, res);
-      bool cok;
       if constexpr (kTwo) {
         // Stereo.  The bank rows in LDS hold ONE channel of one pass at a time: on entry channel 0 of P (banked by the previous
         // iteration or by the cold path).  OUT(P, 0) above has gathered them; now BANK(P, 1) -> OUT(P, 1) -> BANK(N, 0), each after
@@ -918,7 +1044,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, P.ws - wbase - 31, l, 1);
         out_pass(mode_tag, P, res1, 1);
         asm volatile("" : "+v"(res1[0]), "+v"(res1[1]));
-        place_next();
+        place_next(std::false_type{}, PlaceRecs{});
         const int offs = wsK - 31;
         bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, offs, l, 0);
         const bool c0 = s3_convert_ch(L, conv_next, l, 0, true);
@@ -939,6 +1065,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         fetch_records((pk + 2) & 3, rbC);
         chunk_dma(dma_next);
         store_pass(P, res);
+      }
       }
       wave_lds_fence();
       ++conv_next;

@@ -182,8 +182,16 @@ __device__ __noinline__ float2 sinc_two_f64(double p, double dp, const float* __
 // partial sums meet in a butterfly over the f lanes.  Same per-tap arithmetic as sinc_one_f64 (util/resampling.py:66-90); the
 // order of the float64 sum differs (1e-16 of the result, which is then rounded to float32).
 // want: this lane has a slow output (p, dp); returns its two channels' values (.y unused for NCH = 1) in the lanes that want.
+// (PAR_COLD_FN: how the two float64 cold functions of this header are emitted.  Out of line they keep the block kernels' hot
+// code small; each then saves a callee-saved register on the stack, and every kernel that can reach them gets a private
+// segment for it.  The streaming kernels (sinc2.hip), which reach them from their end tiles only, take them inline instead.)
+#ifdef PAR_COLD_FN
+#define PAR_COLD_FN_GIVEN 1      // (the includer checks this: the header may have been seen earlier, before its definition)
+#else
+#define PAR_COLD_FN __noinline__
+#endif
 template <int NCH>
-__device__ __noinline__ float2 sinc_slow_wave(bool want, double p, double dp, const float* __restrict__ sig,
+__device__ PAR_COLD_FN float2 sinc_slow_wave(bool want, double p, double dp, const float* __restrict__ sig,
                                               const float* __restrict__ sig1, int64_t sig_stride, int64_t len_in, int NT, int l) {
   const unsigned long long mask = __ballot(want);
   const int n = __popcll(mask);
@@ -935,7 +943,7 @@ struct PosDp {
 };
 // A lazy plan (pos_plan.h) holds no checkpoints (ckp == nullptr): the walk starts at the segment's first step (<= kLazyMaxN
 // of them; ~1 output in 10^6 comes here).
-__device__ __noinline__ PosDp place_exact(const double* __restrict__ speeds, const int64_t* __restrict__ seg_start,
+__device__ PAR_COLD_FN PosDp place_exact(const double* __restrict__ speeds, const int64_t* __restrict__ seg_start,
                                           const double* __restrict__ seg_off, const double* __restrict__ ckp, long long i,
                                           long long j, long long len_out) {
 #pragma clang fp contract(off)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-stage instruction census of the streaming kernel's two hot loops (fc = 1 and fc < 1), from the compiler's listing.
     python tools/isa_census.py [NCH [KIND]] [extra hipcc flags]   -> prints the table committed as profiles/r06_isa_census.txt
+    python tools/isa_census.py --waits [NCH [KIND]] [flags]       -> per hot loop, every LDS read with the first s_waitcnt lgkmcnt
+                                                                     that covers it and the wave's own vector work in between
 Every instruction between a loop's `s_waitcnt vmcnt(N)` head and its back edge is attributed to the STAGE its .loc source
 line belongs to (source ranges of sinc2.hip named below; inlined header code is charged to the last csrc line seen)."""
 import os, re, subprocess, sys, tempfile
@@ -22,10 +24,17 @@ def stage_table(src):
                 return i + 1
     T = []
     for name, pat in (("place_row", r"S2Row s2_place_row"), ("bank", r"void bank_image3m"), ("out_row", r"float s3_out_row"),
+                      ("bank", r"S3Frags bank_load"), ("bank", r"void bank_math"), ("out_row", r"S3Gather s3_out_load"),
+                      ("out_row", r"float s3_out_math"), ("convert", r"float2 s3_convert_load"), ("convert", r"bool s3_convert_math"),
                       ("convert", r"bool s3_convert\("), ("convert", r"bool s3_convert_ch\("), ("out_row", r"float sinpi_poly")):
-        a = find(r"__device__ __forceinline__ " + pat) if "S2Row" not in pat else find(pat)
+        try:
+            a = find(r"__device__ __forceinline__ " + pat) if "S2Row" not in pat else find(pat)
+        except KeyError:          # (a source from before the load / arithmetic halves: PAR_CSRC below)
+            continue
         T.append((a - 1, end_of(a), name))
-    a = find(r"auto place = \[&\]"); b = find(r"^\s*S3Pass P;", a)
+    try: a = find(r"struct PlaceRecs")
+    except KeyError: a = find(r"auto place = \[&\]")
+    b = find(r"^\s*S3Pass P;", a)
     T.append((a, b, "place"))
     a = find(r"auto place_next = \[&\]"); b = find(r"^\s*};", a)
     T.append((a, b, "place_next"))
@@ -59,14 +68,46 @@ def port_cycles(l):
     if re.search(r"(?<![\w\[])s\d+|s\[\d+:\d+\]|\bvcc\b|\bexec\b|\bm0\b", src): return 4.3
     return 2.4
 
-def main():
-    nch = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].isdigit() else "1"
-    kind = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2].isdigit() else ("2" if nch == "1" else "0")
-    dump = next((a[7:] for a in sys.argv[1:] if a.startswith("--dump=")), None)     # --dump=STAGE: list that stage's instructions
-    extra = [a for a in sys.argv[1:] if not a.isdigit() and not a.startswith("--dump=")]
+def waits_rows(L, h, back, files, stages):
+    """--waits: LDS operations complete in order, so `s_waitcnt lgkmcnt(n)` covers every LDS operation but the last n issued.
+    For each LDS read of the loop body (listing order, both placement variants in line): the first such wait behind it that
+    covers it, and what the wave itself offers the vector port in between (instructions, priced port cycles)."""
+    cur, last_stage = ("?", 0), "loop"
+    pend = []                      # LDS operations in flight: [is_read, listing line, text, stage, vector instrs since, port cycles since]
+    rows = []
+    for i in range(h, back + 1):
+        l = L[i].strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", l)
+        if m: cur = (files.get(int(m.group(1)), "?"), int(m.group(2))); continue
+        if not l or l.startswith((";", ".", "//")) or l.endswith(":"): continue
+        op = l.split()[0]
+        if cur[0] == "sinc2.hip": last_stage = next((n for a, b, n in stages if a <= cur[1] <= b), "loop")
+        if op == "s_waitcnt":
+            m = re.search(r"lgkmcnt\((\d+)\)", l)
+            if m:
+                n = int(m.group(1))
+                done, pend = (pend[:len(pend) - n], pend[len(pend) - n:]) if n < len(pend) else ([], pend)
+                rows += [(p[1], p[2], p[3], i + 1, n, p[4], p[5]) for p in done if p[0]]
+            continue
+        pc = port_cycles(l)
+        if op.startswith("v_"):
+            for p in pend: p[4] += 1; p[5] += pc
+        if op.startswith("ds_"):
+            pend.append([bool(re.match(r"ds_(read|load)", op)), i + 1, " ".join(l.split()[:2]).rstrip(","), last_stage, 0, 0.0])
+    rows += [(p[1], p[2], p[3], None, None, p[4], p[5]) for p in pend if p[0]]
+    return sorted(rows, key=lambda r: r[0])      # (listing line, read, stage, line of the wait, its lgkmcnt, vector instrs, port cycles)
+
+def waits_table(L, h, back, files, stages):
+    rows = waits_rows(L, h, back, files, stages)
+    print(f"{'line':>7s}  {'read':26s} {'stage':10s} {'wait at':>8s} {'lgkmcnt':>7s} {'vector instrs':>13s} {'port cycles':>11s}")
+    for ln, txt, st, wl, n, nv, pc in rows:
+        print(f"{ln:7d}  {txt:26s} {st:10s} " + (f"{wl:8d} {n:7d}" if wl else f"{'(next it.)':>8s} {'':>6s}") + f" {nv:13d} {pc:11.0f}")
+
+def compile_listing(extra=()):
+    """sinc2.hip's gfx950 listing with the project's flags (+ line tables): (lines, {file number: name}, stage table)"""
     tmp = tempfile.mkdtemp()
-    src = os.path.join(B.CSRC, "sinc2.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + B.FLAGS + B.PER_FILE.get("sinc2.hip", []) + extra +
+    src = os.path.join(os.environ.get("PAR_CSRC", B.CSRC), "sinc2.hip")      # PAR_CSRC: another checkout's csrc (a parent's table)
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + B.FLAGS + B.PER_FILE.get("sinc2.hip", []) + list(extra) +
                           ["-gline-tables-only", "-save-temps", "-c", src, "-o", os.path.join(tmp, "o.o")], cwd=tmp,
                           stderr=subprocess.DEVNULL)
     s = next(os.path.join(tmp, f) for f in os.listdir(tmp) if f.endswith("gfx950.s") and f.startswith("sinc2"))
@@ -75,20 +116,47 @@ def main():
     for l in L:
         m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
         if m: files[int(m.group(1))] = os.path.basename(m.group(3) or m.group(2))
+    return L, files, stage_table(src)
+
+def kernel_loops(L, nch, kind):
+    """k_sinc_pipe<nch, kind> in the listing: ({NumVgprs, ScratchSize, Occupancy, ...}, [(first, last listing line) of each hot loop])"""
     start = next(i for i, l in enumerate(L) if re.match(r"^_ZN3par11k_sinc_pipeILi%sELi%sEEE" % (nch, kind), l))
     end = next(i for i in range(start, len(L)) if L[i].startswith(".Lfunc_end"))
+    info = {}
     for i in range(end, min(end + 60, len(L))):
-        if re.search(r"; (NumVgprs|NumAgprs|ScratchSize|Occupancy|NumSgprs|LDSByteSize)", L[i]): print(L[i].strip())
-    stages = stage_table(src)
+        m = re.search(r"; (NumVgprs|NumAgprs|ScratchSize|Occupancy|NumSgprs|LDSByteSize): (\d+)", L[i])
+        if m and m.group(1) not in info: info[m.group(1)] = (int(m.group(2)), L[i].strip())
     heads = [i for i in range(start, end) if re.search(r"s_waitcnt vmcnt\((5|7)\)", L[i])]
-    for hi, h in enumerate(heads):
+    loops = []
+    for h in heads:
         # loop header: the nearest "Parent Loop" label above the head; body: every block that names it as its header
         hl = next(i for i in range(h, start, -1) if re.match(r"^\.LBB\d+_\d+:.*Parent Loop", L[i]))
         lab = L[hl].split(":")[0].lstrip(".L")
         # the latch is the block in front of the header (it falls through into it); the body ends at the last branch to the latch
         latch = next(L[i].split(":")[0] for i in range(hl - 1, start, -1) if re.match(r"^\.LBB\d+_\d+:", L[i]))
         back = max(i for i in range(hl, end) if re.search(r"s_c?branch\w*\s+%s\b" % re.escape(latch), L[i]))
-        h = hl
+        loops.append((hl, back))
+    return info, loops
+
+def main():
+    waits = "--waits" in sys.argv
+    if waits: sys.argv.remove("--waits")
+    nch = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].isdigit() else "1"
+    kind = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2].isdigit() else ("2" if nch == "1" else "0")
+    dump = next((a[7:] for a in sys.argv[1:] if a.startswith("--dump=")), None)     # --dump=STAGE: list that stage's instructions
+    extra = [a for a in sys.argv[1:] if not a.isdigit() and not a.startswith("--dump=")]
+    L, files, stages = compile_listing(extra)
+    info, loops = kernel_loops(L, nch, kind)
+    for k in ("NumVgprs", "NumAgprs", "ScratchSize", "LDSByteSize", "Occupancy"):
+        if k in info: print(info[k][1])
+    for hi, (h, back) in enumerate(loops):
+        if waits:
+            n_mfma = sum(1 for i in range(h, back + 1) if L[i].strip().startswith("v_mfma"))
+            what = "fc = 1" if n_mfma <= 16 else ("fc < 1, order 5" if n_mfma <= 29 else "fc < 1, order 6")
+            print(f"\nloop {hi} ({what}): listing lines {h}..{back}, heads (s_waitcnt vmcnt) in the body: "
+                  f"{sum(1 for i in range(h, back + 1) if re.search(r's_waitcnt.*vmcnt', L[i]))}")
+            waits_table(L, h, back, files, stages)
+            continue
         cur, last_stage = ("?", 0), "loop"
         tab = {}
         for i in range(h, back + 1):
