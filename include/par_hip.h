@@ -490,6 +490,32 @@ int64_t par_gate_stft_transformed_frames(int64_t n, int n_fft, int hop);
  * numerator of the selection profile np.average(mag[:, f0:f1], axis=1) (renoiser_gui.py:340). */
 int par_mean_mag_frames_f32(int device, const float* mag, int64_t n_frames, int64_t bins, int64_t mag_pitch, double* acc,
                             void* stream);
+
+/* ---- harmonic / percussive separation (util/decompose.py, experiments/hpss_gui.py), ABI 109 ---------------------------------- */
+/* decompose.hpss on a frame-major spectrogram (DEVICE spec[n_frames][pitch], pitch 0 = bins; is_complex != 0: complex64, the
+ * layout par_stft_f32 mode 0 and par_stft_big_f32 mode 0 write, else float32 magnitudes, read through fabs).  Per bin:
+ *   harm = scipy.ndimage.median_filter(|S|, win_harm, mode="reflect") along frames, perc = the same over win_perc along bins
+ *          (window offsets -(k/2) .. k-1-k/2, the element of rank k/2, half-sample symmetric reflection repeated as often as
+ *          the axis needs; 1 <= k <= PAR_HPSS_MAX_KERNEL, odd or even).  |S| is numpy's complex64 np.abs (see
+ *          par_gate_spectrum_f32, without its + 1e-7): the medians are selections and equal scipy's on np.abs(spec) bit for bit.
+ *   mask_h = softmask(harm, perc * margin_h), mask_p = softmask(perc, harm * margin_p) in float32: Z = max(X, Xref);
+ *          Z < FLT_MIN -> 0.5 when both margins are 1, else 0; else (X/Z)^power / ((X/Z)^power + (Xref/Z)^power) (power 2
+ *          squares, 1 and 0.5 are exact too); power = +inf: the hard mask X > Xref.
+ * out_kind PAR_HPSS_COMPONENTS: out_h = S * mask_h, out_p = S * mask_p (the input's type);  PAR_HPSS_MASKS: the two float32 masks;
+ * PAR_HPSS_HARMONIC: out_h = S * mask_h only (out_p may be NULL; decompose.harmonic);  PAR_HPSS_MEDIANS: float32 harm and perc.
+ * Outputs are DEVICE [n_frames][pitch] arrays of their element type and must not overlap spec or each other.  No scratch.
+ * Kernel sizes outside 1..99, power <= 0 (or NaN), a margin below 1 and null pointers: PAR_ERR_ARG before any device call. */
+#define PAR_HPSS_MAX_KERNEL 99
+#define PAR_HPSS_COMPONENTS 0
+#define PAR_HPSS_MASKS 1
+#define PAR_HPSS_HARMONIC 2
+#define PAR_HPSS_MEDIANS 3
+int par_hpss_f32(int device, const void* spec, int is_complex, int64_t n_frames, int64_t bins, int64_t pitch, int win_harm,
+                 int win_perc, double power, double margin_h, double margin_p, void* out_h, void* out_p, int out_kind, void* stream);
+/* r[i * r_stride] = x[i * x_stride] - (h[i * h_stride] + p[i * p_stride]), i < n, float32 (DEVICE; the residual of
+ * hpss_gui.py:145 on channel views of interleaved signals). */
+int par_residual_f32(int device, const float* x, int64_t x_stride, const float* h, int64_t h_stride, const float* p,
+                     int64_t p_stride, int64_t n, float* r, int64_t r_stride, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -9,5 +9,5 @@ library or without a GPU every compute entry point raises.
 from . import _lib  # noqa: F401
 from ._lib import ParError, ParUnsupported, ParIndexError, ParShapeError, ParEmptyBand  # noqa: F401
 
-__all__ = ["fourier", "resampling", "wow_detection", "filters", "correlation", "pipeline", "io_ops", "spectrum_flat", "expander", "renoiser",
+__all__ = ["fourier", "resampling", "wow_detection", "filters", "correlation", "pipeline", "io_ops", "spectrum_flat", "expander", "renoiser", "decompose", "hpss",
            "ParError", "ParUnsupported", "ParIndexError", "ParShapeError", "ParEmptyBand"]

@@ -1,8 +1,8 @@
 """Builds libpar_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 Each csrc/*.hip is compiled to an object with per-file flags, then linked.  pos.hip (float64
-positions that must be bit-identical to numpy) and expander.hip (numpy's interpolation, compensated sums) are built with
--ffp-contract=off; the other kernels
+positions that must be bit-identical to numpy), expander.hip (numpy's interpolation, compensated sums) and hpss.hip (numpy's
+float32 soft mask) are built with -ffp-contract=off; the other kernels
 keep hipcc's default contraction and spell their FMAs explicitly."""
 import glob
 import os
@@ -17,6 +17,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 PER_FILE = {"pos.hip": ["-ffp-contract=off"],
             "lag.hip": ["-ffp-contract=off"],
             "expander.hip": ["-ffp-contract=off"],
+            "hpss.hip": ["-ffp-contract=off"],
             # SLP packing into v_pk_*_f32 buys no throughput on gfx950 and costs v_mov shuffles
             "sinc.hip": ["-fno-slp-vectorize"],
             "sinc2.hip": ["-fno-slp-vectorize"],

@@ -12,6 +12,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli heal --project tape.drop tape.flac
     python -m pyaudiorestoration_amd.cli expand --channels L+R --clip -120,-85 tape.wav     # Spectral Expander -> tape_decompressed.wav
     python -m pyaudiorestoration_amd.cli renoise --noise hiss.wav tape.wav                  # renoiser -> "tape fft=2048.wav"
+    python -m pyaudiorestoration_amd.cli hpss --kernel 31,17 --margin 2,3 take.flac         # -> take_H.wav, take_P.wav, take_R.wav
 """
 import argparse
 import json
@@ -29,7 +30,7 @@ def _worker(dev, jobs, args, results):
     release the GIL) on a helper thread while the current one is on the GPU."""
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    from . import _dev, expander, io_ops, pipeline, renoiser, resampling
+    from . import _dev, expander, hpss, io_ops, pipeline, renoiser, resampling
     torch.cuda.set_device(dev)
 
     def take():
@@ -65,6 +66,11 @@ def _worker(dev, jobs, args, results):
                 if args.cmd == "renoise":
                     renoiser.renoise_file(path, args.noise, args.select, args.fft, args.overlap, args.gain, args.overhead, args.curve,
                                           args.channels, device=dev, signal_data=(signal, sr, ch))
+                    results.append((path, None))
+                    continue
+                if args.cmd == "hpss":
+                    hpss.separate_file(path, args.fft, args.overlap, args.kernel, args.power, args.margin, device=dev,
+                                       signal_data=(signal, sr, ch))
                     results.append((path, None))
                     continue
                 quality = 50 if args.quality is None else args.quality          # the GUI's default (util/widgets.py:998-1000)
@@ -142,6 +148,22 @@ def parser():
     r.add_argument("--channels", type=ints, default=None, help="channel numbers, e.g. 0,1 (default: all)")
     r.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
     r.add_argument("files", nargs="+")
+
+    def one_or_two(kind):
+        def parse(s):
+            v = [kind(x) for x in s.split(",")]
+            if len(v) not in (1, 2):
+                raise argparse.ArgumentTypeError(f"one value or two (harmonic,percussive): {s!r}")
+            return v[0] if len(v) == 1 else tuple(v)
+        return parse
+    h = sub.add_parser("hpss", help="harmonic / percussive separation by median filtering: <stem>_H.wav, _P.wav (and _R.wav)")
+    h.add_argument("--fft", type=int, default=512, help="FFT size")
+    h.add_argument("--overlap", type=int, default=4, help="hop = fft / overlap")
+    h.add_argument("--kernel", type=one_or_two(int), default=(31, 31), help="median sizes HARMONIC,PERCUSSIVE (1..99; one value: both)")
+    h.add_argument("--power", type=float, default=2.0, help="exponent of the soft mask (inf: hard mask)")
+    h.add_argument("--margin", type=one_or_two(float), default=1.0, help="mask margin(s) >= 1; other than 1 also writes the residual")
+    h.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
+    h.add_argument("files", nargs="+")
     return ap
 
 
