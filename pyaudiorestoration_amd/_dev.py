@@ -1,7 +1,7 @@
 """Device plumbing: PyTorch-ROCm is used ONLY to own HBM buffers and name streams."""
 import ctypes
 import threading
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import ThreadPoolExecutor, wait
 
 import numpy as np
 import torch
@@ -37,25 +37,38 @@ _stage = {}
 _stage_lock = threading.Lock()
 
 
+def _pool():
+    with _stage_lock:
+        if "pool" not in _stage:
+            _stage["pool"] = ThreadPoolExecutor(max_workers=4, thread_name_prefix="par_stage")
+        return _stage["pool"]
+
+
 def _stage_state(dev, kind):
-    st = _stage.get((dev, kind))
-    if st is None:
-        ring = [torch.empty(_STAGE_CHUNK, dtype=torch.uint8).pin_memory() for _ in range(_STAGE_RING)]
-        st = _stage[(dev, kind)] = {"ring": ring, "np": [r.numpy() for r in ring], "busy": threading.Lock()}
-    if "pool" not in _stage:
-        _stage["pool"] = ThreadPoolExecutor(max_workers=4, thread_name_prefix="par_stage")
-    return st
+    with _stage_lock:
+        st = _stage.get((dev, kind))
+        if st is None:
+            ring = [torch.empty(_STAGE_CHUNK, dtype=torch.uint8).pin_memory() for _ in range(_STAGE_RING)]
+            st = _stage[(dev, kind)] = {"ring": ring, "np": [r.numpy() for r in ring], "busy": threading.Lock()}
+    return st, _pool()
+
+
+def _release_after(futs, st):
+    for f in futs:                                         # (a failed transfer: what has not started never will)
+        f.cancel()
+    wait(futs)                                             # the ring is handed on only once nothing submitted can touch its chunks
+    st["busy"].release()
 
 
 def _h2d_staged(src, dst, dev):
     """src: contiguous numpy array, dst: contiguous device tensor of the same byte size -> False when the ring is in use."""
-    with _stage_lock:
-        st = _stage_state(dev, "up")
+    st, pool = _stage_state(dev, "up")
     if not st["busy"].acquire(blocking=False):
         return False
+    futs = []
     try:
         src_u8, dst_u8 = src.reshape(-1).view(np.uint8), dst.view(-1).view(torch.uint8)
-        n, C, R, pool = src_u8.size, _STAGE_CHUNK, _STAGE_RING, _stage["pool"]
+        n, C, R = src_u8.size, _STAGE_CHUNK, _STAGE_RING
         stream = torch.cuda.current_stream(dev)
         events = [None] * R
 
@@ -67,11 +80,9 @@ def _h2d_staged(src, dst, dev):
             np.copyto(st["np"][b][:hi - lo], src_u8[lo:hi])
             return lo, hi, b
         nch = -(-n // C)
-        futs, submitted = [None] * nch, 0
         for k in range(nch):
-            while submitted < nch and submitted < k + R:   # fills run at most R chunks ahead of the copies issued: chunk j - R has its event
-                futs[submitted] = pool.submit(fill, submitted)
-                submitted += 1
+            while len(futs) < min(nch, k + R):             # fills run at most R chunks ahead of the copies issued: chunk j - R has its event
+                futs.append(pool.submit(fill, len(futs)))
             lo, hi, b = futs[k].result()
             dst_u8[lo:hi].copy_(st["ring"][b][:hi - lo], non_blocking=True)
             ev = torch.cuda.Event()
@@ -82,25 +93,24 @@ def _h2d_staged(src, dst, dev):
                 ev.synchronize()                           # the ring may be refilled by the next call
         return True
     finally:
-        st["busy"].release()
+        _release_after(futs, st)
 
 
 def _d2h_staged(src, dst, dev):
     """src: contiguous device tensor, dst: contiguous numpy array of the same byte size -> False when the ring is in use."""
-    with _stage_lock:
-        st = _stage_state(dev, "down")
+    st, pool = _stage_state(dev, "down")
     if not st["busy"].acquire(blocking=False):
         return False
+    futs = []
     try:
         src_u8, dst_u8 = src.view(-1).view(torch.uint8), dst.reshape(-1).view(np.uint8)
-        n, C, R, pool = dst_u8.size, _STAGE_CHUNK, _STAGE_RING, _stage["pool"]
+        n, C, R = dst_u8.size, _STAGE_CHUNK, _STAGE_RING
         stream = torch.cuda.current_stream(dev)
 
         def drain(lo, hi, b, ev):
             ev.synchronize()
             np.copyto(dst_u8[lo:hi], st["np"][b][:hi - lo])
         nch = -(-n // C)
-        futs = [None] * nch
         for k in range(nch):
             b, lo = k % R, k * C
             hi = min(n, lo + C)
@@ -109,12 +119,12 @@ def _d2h_staged(src, dst, dev):
             st["ring"][b][:hi - lo].copy_(src_u8[lo:hi], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(stream)
-            futs[k] = pool.submit(drain, lo, hi, b, ev)
+            futs.append(pool.submit(drain, lo, hi, b, ev))
         for f in futs[max(0, nch - R):]:
             f.result()
         return True
     finally:
-        st["busy"].release()
+        _release_after(futs, st)
 
 
 def host_copy(dst, src):
@@ -127,19 +137,8 @@ def host_copy(dst, src):
     if d.size < (8 << 20):
         np.copyto(d, s)
         return
-    with _stage_lock:
-        if "pool" not in _stage:
-            _stage["pool"] = ThreadPoolExecutor(max_workers=4, thread_name_prefix="par_stage")
-        pool = _stage["pool"]
     step = -(-d.size // 8) + 63 & ~63
-    list(pool.map(lambda lo: np.copyto(d[lo:lo + step], s[lo:lo + step]), range(0, d.size, step)))
-
-
-def _pool():
-    with _stage_lock:
-        if "pool" not in _stage:
-            _stage["pool"] = ThreadPoolExecutor(max_workers=4, thread_name_prefix="par_stage")
-        return _stage["pool"]
+    list(_pool().map(lambda lo: np.copyto(d[lo:lo + step], s[lo:lo + step]), range(0, d.size, step)))
 
 
 def host_assign(dst, src):

@@ -144,22 +144,9 @@ def respeed(signal, sr, trail, fft_size=1024, hop=256, zeropad=1, mode="Peak", t
     pos_t = resampling.speed_to_pos_dev(st_t, sp_t, n, dev)      # kept: the GUI shows / reuses sample_at
     plan = resampling.speed_plan_dev(st_t, sp_t, n, dev, fused=True) if resampling_mode == "Sinc" else None
     out_t = _dev.empty((pos_t.numel(), ch), torch.float32, dev)
-    flat_in, flat_out = sig_t.reshape(-1), out_t.reshape(-1)
-    layout = dict(sig_stride=ch, len_in=n, out_stride=ch)
-    c = 0
-    while c < ch:
-        if resampling_mode == "Sinc" and plan.fused_ok and c + 1 < ch:      # channel pairs share one stereo launch
-            resampling.varispeed_fused_stereo_dev(plan, flat_in[c:], flat_in[c + 1:], sinc_quality, flat_out[c:],
-                                                  flat_out[c + 1:], **layout)
-            c += 2
-            continue
-        if resampling_mode == "Sinc" and plan.fused_ok:
-            resampling.varispeed_fused_dev(plan, flat_in[c:], sinc_quality, flat_out[c:], **layout)
-        elif resampling_mode == "Sinc":
-            resampling.sinc_resample_dev(pos_t, flat_in[c:], sinc_quality, flat_out[c:], dev=dev, **layout)
-        else:
-            resampling.linear_resample_dev(pos_t, flat_in[c:], flat_out[c:], dev=dev, **layout)
-        c += 1
+    resampling.resample_channels(sig_t.reshape(-1), out_t.reshape(-1), [(c, c) for c in range(ch)],
+                                 dict(sig_stride=ch, len_in=n, out_stride=ch), sinc_quality,
+                                 "Sinc" if resampling_mode == "Sinc" else "Linear", plan, pos_t)     # (any other mode: linear)
     return {"spectrum": spec, "times": track.times, "freqs": track.freqs, "speed_curve": curve, "positions": pos_t,
             "output": out_t}
 

@@ -8,7 +8,7 @@ import ctypes
 import logging
 import os
 import threading
-from time import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -171,46 +171,83 @@ def varispeed_fused_stereo_dev(plan, sig0_t, sig1_t, NT, out0_t, out1_t, sig_str
     return out0_t, out1_t
 
 
+class WorkItem(NamedTuple):
+    """One file of a batch.  A 2-D sig_t is an interleaved (n, ch) file: sig_stride = ch, len_in = n."""
+    st_t: torch.Tensor
+    sp_t: torch.Tensor
+    sig_t: torch.Tensor
+    sig_stride: int
+    len_in: int
+
+    @property
+    def cls(self):
+        """Items whose K_sinc launches par_varispeed_fused_batch_f32 can merge: 'mono' (1-D, unit stride), 'stereo' (an
+        interleaved (n, 2) file); None: launched on its own."""
+        if self.sig_t.ndim == 2:
+            return "stereo" if self.sig_t.shape[1] == 2 and self.sig_t.is_contiguous() else None
+        return "mono" if self.sig_stride == 1 else None
+
+    @property
+    def n_samples(self):
+        return self.sig_t.numel()
+
+
+def work_item(item):
+    """WorkItem from what callers hand over: (st_t, sp_t, sig_t[, sig_stride[, len_in]]) or a WorkItem."""
+    if isinstance(item, WorkItem):
+        return item
+    st_t, sp_t, sig_t = item[:3]
+    if sig_t.ndim == 2:
+        return WorkItem(st_t, sp_t, sig_t, sig_t.shape[1], sig_t.shape[0])
+    stride = item[3] if len(item) > 3 else 1
+    return WorkItem(st_t, sp_t, sig_t, stride, item[4] if len(item) > 4 else sig_t.numel() // stride)
+
+
+def resample_channels(flat_in, flat_out, channels, layout, NT, mode, plan=None, pos_t=None, progress=lambda value: None):
+    """The channel loop of one file on flat views of its interleaved input and output; channels: (input channel, output column)
+    pairs, layout: dict(sig_stride, len_in, out_stride).  "Sinc" from a plan with valid checkpoints: consecutive pairs share one
+    stereo launch (positions, hence the whole weight computation, are common), an odd one out goes alone; "Sinc" otherwise and
+    "Linear" read pos_t; any other mode launches nothing.  progress receives k / n * 100 for every channel k = 1..n done."""
+    n, k = len(channels), 0
+    fused = mode == "Sinc" and plan is not None and plan.fused_ok
+    while k < n:
+        (c_in, c_out), pair = channels[k], fused and k + 1 < n
+        if pair:
+            c_in1, c_out1 = channels[k + 1]
+            varispeed_fused_stereo_dev(plan, flat_in[c_in:], flat_in[c_in1:], NT, flat_out[c_out:], flat_out[c_out1:], **layout)
+        elif fused:
+            varispeed_fused_dev(plan, flat_in[c_in:], NT, flat_out[c_out:], **layout)
+        elif mode == "Sinc":
+            sinc_resample_dev(pos_t, flat_in[c_in:], NT, flat_out[c_out:], **layout)
+        elif mode == "Linear":
+            linear_resample_dev(pos_t, flat_in[c_in:], flat_out[c_out:], **layout)
+        for k in range(k + 1, k + 2 + pair):               # (leaves k at the next channel)
+            progress(k / n * 100)
+
+
 def _resample_item(plan, item, NT, dev):
     """K_sinc launch(es) of one planned work item on the current stream: (.., sig_t[, sig_stride, len_in]) with a 1-D
     sig_t, or an interleaved (n, ch) sig_t whose channel pairs share one stereo launch (an odd last channel goes
     alone).  A plan without valid checkpoints takes the position-array path."""
-    sig_t = item[2]
+    item = work_item(item)
+    sig_t = item.sig_t
     if sig_t.ndim == 2:
-        n_in, ch = sig_t.shape
+        ch = item.sig_stride
         out_t = _dev.empty((plan.len_out, ch), torch.float32, dev)
-        flat_in, flat_out = sig_t.reshape(-1), out_t.reshape(-1)
-        layout = dict(sig_stride=ch, len_in=n_in, out_stride=ch)
+        pos_t = None
         if not plan.fused_ok:
             pos_t = _dev.empty(plan.len_out, torch.float64, dev)
             _lib.check(_lib.lib().par_speed_to_pos_fill(dev, _dev.ptr(plan.speeds_t), plan.m, _dev.ptr(plan.work),
                                                         _dev.ptr(pos_t), plan.len_out, _dev.stream_ptr(dev)))
-        c = 0
-        while c < ch:
-            if plan.fused_ok and c + 1 < ch:
-                varispeed_fused_stereo_dev(plan, flat_in[c:], flat_in[c + 1:], NT, flat_out[c:], flat_out[c + 1:], **layout)
-                c += 2
-            elif plan.fused_ok:
-                varispeed_fused_dev(plan, flat_in[c:], NT, flat_out[c:], **layout)
-                c += 1
-            else:
-                sinc_resample_dev(pos_t, flat_in[c:], NT, flat_out[c:], dev=dev, **layout)
-                c += 1
+        resample_channels(sig_t.reshape(-1), out_t.reshape(-1), [(c, c) for c in range(ch)],
+                          dict(sig_stride=ch, len_in=item.len_in, out_stride=ch), NT, "Sinc", plan, pos_t)
         return out_t
-    stride = item[3] if len(item) > 3 else 1
-    len_in = item[4] if len(item) > 4 else sig_t.numel() // stride
     if plan.fused_ok:
-        return varispeed_fused_dev(plan, sig_t, NT, sig_stride=stride, len_in=len_in)
-    return varispeed_resample_dev(plan, sig_t, NT, sig_stride=stride, len_in=len_in)[0]
+        return varispeed_fused_dev(plan, sig_t, NT, sig_stride=item.sig_stride, len_in=item.len_in)
+    return varispeed_resample_dev(plan, sig_t, NT, sig_stride=item.sig_stride, len_in=item.len_in)[0]
 
 
-def _group_class(item):
-    """Items whose K_sinc launches par_varispeed_fused_batch_f32 can merge: 'mono' (1-D, unit stride), 'stereo' (an interleaved
-    (n, 2) file); None: launched on its own."""
-    sig_t = item[2]
-    if sig_t.ndim == 2:
-        return "stereo" if sig_t.shape[1] == 2 and sig_t.is_contiguous() else None
-    return "mono" if len(item) <= 3 or item[3] == 1 else None
+_GROUP_AUTO = 4                     # the largest group the driver forms by itself (_group_size)
 
 
 def _group_size(item):
@@ -221,10 +258,46 @@ def _group_size(item):
     of a plan, ~0.2 ms per file, bounds short files); stereo files LOSE (archive 182 -> 178 in pairs, 170 in fours: the plans
     of a group start together and then compete with one long launch instead of slipping into the gaps between short ones); so
     do 60-min files.  Hence: stereo and long mono files one by one, other mono files four at a time."""
-    sig_t = item[2]
-    if sig_t.ndim == 2 or sig_t.numel() >= 400_000_000:
-        return 1
-    return 4
+    return _GROUP_AUTO if item.cls == "mono" and item.n_samples < 400_000_000 else 1
+
+
+def _lookahead(P, g):
+    """Items taken ahead with P planners and groups of g.  A group's K_sinc is queued only once the NEXT group's items have been
+    taken as well: whatever their producer queues on the main stream then precedes the long launch and their plans run under it
+    (with g - 1 extra items only, half of the next group's plans started after that launch: archive 165 -> 158 G, r06)."""
+    return P if g <= 1 else max(P + g - 1, 2 * g)
+
+
+def _ring_slots(P, group):
+    """Plan slots of a call: twice the look-ahead of the largest group it can form (`group`, else _GROUP_AUTO)."""
+    return 2 * _lookahead(P, group if group is not None else _GROUP_AUTO)
+
+
+def _int_option(value, env, default, what):
+    """`value`, else the environment variable `env` (unset or empty: `default`), as an integer 1..8."""
+    raw = value if value is not None else (os.environ.get(env) or default)
+    if raw is None:
+        return None
+    try:
+        n = int(raw)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be an integer 1..8, got {raw!r}")
+    if not 1 <= n <= 8:
+        raise ValueError(f"{what} must be an integer 1..8, got {n}")
+    return n
+
+
+def _next_group(waiting, group, done):
+    """The grouping step over the work items taken and not yet launched, oldest first (done: the iterable is exhausted) -> (g, n):
+    the head's group size, and how many leave now: the head and those behind it of its class, at most g; 0: take more first."""
+    cls = waiting[0].cls
+    g = 1 if cls is None else (group if group is not None else _group_size(waiting[0]))
+    if g > 1 and not done and len(waiting) < g:
+        return g, 0
+    n = 1
+    while n < g and n < len(waiting) and waiting[n].cls == cls:
+        n += 1
+    return g, n
 
 
 def _resample_group(plans, group, NT, dev):
@@ -233,18 +306,19 @@ def _resample_group(plans, group, NT, dev):
     arr = (_lib.FusedItem * len(group))()
     outs = []
     for k, (plan, item) in enumerate(zip(plans, group)):
-        sig_t = item[2]
+        item = work_item(item)
+        sig_t = item.sig_t
         f = arr[k]
         f.speeds, f.m, f.work, f.aux = _dev.ptr(plan.speeds_t).value, plan.m, _dev.ptr(plan.work).value, _dev.ptr(plan.aux).value
         f.max_out, f.len_out = plan.max_out, plan.len_out
         if sig_t.ndim == 2:
             out_t = _dev.empty((plan.len_out, 2), torch.float32, dev)
             base, obase = _dev.ptr(sig_t).value, _dev.ptr(out_t).value
-            f.sig0, f.sig1, f.sig_stride, f.len_in = base, base + 4, 2, sig_t.shape[0]
+            f.sig0, f.sig1, f.sig_stride, f.len_in = base, base + 4, 2, item.len_in
             f.out0, f.out1, f.out_stride = obase, obase + 4, 2
         else:
             out_t = _dev.empty(plan.len_out, torch.float32, dev)
-            f.sig0, f.sig1, f.sig_stride, f.len_in = _dev.ptr(sig_t).value, None, 1, (item[4] if len(item) > 4 else sig_t.numel())
+            f.sig0, f.sig1, f.sig_stride, f.len_in = _dev.ptr(sig_t).value, None, 1, item.len_in
             f.out0, f.out1, f.out_stride = _dev.ptr(out_t).value, None, 1
         outs.append(out_t)
     _lib.check(L.par_varispeed_fused_batch_f32(dev, len(group), arr, int(NT), _dev.stream_ptr(dev)))
@@ -277,7 +351,8 @@ def _borrow_plan_ring(dev, n_slots, P):
 
 
 def release_plan_rings():
-    """Free the plan buffers varispeed_batch_dev keeps between calls (2 x lookahead slots of ~1.3 B per output sample each)."""
+    """Free the plan buffers varispeed_batch_dev keeps between calls: per device, the slots of the largest ring a call asked for
+    (16 by default, at most 32) x (work + aux, ~1.3 B per output sample of the largest file that has passed through the slot)."""
     with _plan_rings_lock:
         for dev in [d for d, r in _plan_rings.items() if not r["busy"]]:
             del _plan_rings[dev]
@@ -292,14 +367,16 @@ def varispeed_batch_dev(items, NT, dev=None, planners=None, group=None):
     in the gaps around a K_sinc -- where `planners` of them then advance TOGETHER (they are latency-, not
     throughput-bound).  Measured on 60-min mono files (r05, ms per file): 1 planner 5.0, 2: 4.66, 3: 4.57, 4: 4.63, 8: 4.63
     -- default 3 (PAR_PLANNERS).
-    Plan buffers form a ring of 2 x planners slots; an event keeps a slot from being re-planned before the K_sinc
-    that reads it has finished.  planners=1 is the double-buffered pipeline of r02-r04.
+    Plan buffers form a ring of _ring_slots(planners, group) slots, twice the look-ahead below (16 by default, 32 with group=8,
+    2 x planners with group=1); an event keeps a slot from being re-planned before the K_sinc that reads it has finished.
+    Memory: slots x (work + aux), each pair sized to the largest file that has passed through its slot (~1.3 B per output
+    sample, 0.9 GB for a 60-min file), kept BETWEEN calls as well (release_plan_rings() frees them).  A yielded SpeedPlan
+    ALIASES its slot's buffers: it is valid only until the ring wraps (the item `slots` behind it is taken from the iterable,
+    up to look-ahead items before that one's turn) or the next call on that device.
 
     PREFETCH CONTRACT: `planners` items (default 3) are taken from the iterable AHEAD of the one being resampled, and their
     tensors are read until that item's output has been yielded -- a producer that recycles its input tensors needs a ring of
-    at least planners + 1 of them (planners=1 is the one-ahead contract of r02-r04).  Memory: 2 x planners plan / aux buffer
-    pairs, each sized for the eager plan's checkpoints (~1.3 B per output sample: 0.9 GB for a 60-min file), stay allocated
-    BETWEEN calls as well (release_plan_rings() frees them).
+    at least planners + 1 of them (planners=1, group=1 is the one-ahead, double-buffered pipeline of r02-r04).
 
     GROUPS (r06): consecutive items of one class -- mono on unit strides, or interleaved stereo files -- are resampled by ONE merged
     K_sinc launch per group (par_varispeed_fused_batch_f32; default: mono files below 400 M samples four at a time, everything
@@ -308,55 +385,30 @@ def varispeed_batch_dev(items, NT, dev=None, planners=None, group=None):
     items are yielded together once its launch has been queued.  The prefetch contract grows to max(planners + group - 1, 2 x group)
     items taken ahead (the next group is planned under the launch of this one): a recycling producer needs that many + group tensors.
 
-    items: iterable of (sampletimes_t, speeds_t, sig_t) or (sampletimes_t, speeds_t, sig_t, sig_stride, len_in)
-    with float64 / float32 device tensors; a 2-D sig_t is an interleaved (n, ch) file whose channels share the plan
-    (channel pairs go through the stereo launch) and yields an (len_out, ch) output.  Up to `planners` items are
-    taken from the iterable ahead of the one being resampled (their tensors stay resident meanwhile).  Yields
-    (index, out_t, plan) in order; out_t is ready on the current stream (synchronise or keep using that stream).
-    An item whose plan cannot feed the fused resampler is resampled through the position-array path."""
+    items: iterable of (sampletimes_t, speeds_t, sig_t[, sig_stride[, len_in]]) with float64 / float32 device tensors (work_item);
+    a 2-D sig_t is an interleaved (n, ch) file whose channels share the plan (channel pairs go through the stereo launch) and
+    yields an (len_out, ch) output.  Yields (index, out_t, plan) in order; out_t is ready on the current stream (synchronise or
+    keep using that stream).  An item whose plan cannot feed the fused resampler is resampled through the position-array path."""
     import collections
     from concurrent.futures import ThreadPoolExecutor
     dev = _dev.device_index(dev)
-    P = planners if planners is not None else os.environ.get("PAR_PLANNERS", "3")
-    try:
-        P = int(P)
-    except (TypeError, ValueError):
-        raise ValueError(f"planners / PAR_PLANNERS must be an integer 1..8, got {P!r}")
-    if not 1 <= P <= 8:
-        raise ValueError(f"planners / PAR_PLANNERS must be an integer 1..8, got {P}")
-    if group is None and os.environ.get("PAR_GROUP"):        # (A/B sessions: 1 = the ungrouped launches of r05)
-        group = os.environ["PAR_GROUP"]
-    try:
-        group = None if group is None else int(group)
-    except (TypeError, ValueError):
-        raise ValueError(f"group / PAR_GROUP must be an integer 1..8, got {group!r}")
-    if group is not None and not 1 <= group <= 8:
-        raise ValueError(f"group / PAR_GROUP must be an integer 1..8, got {group!r}")
-    G_max = int(group) if group is not None else 8
-    def lookahead(g):
-        # a group's K_sinc is queued only once the NEXT group's items have been taken as well: whatever their producer queues on
-        # the main stream then precedes the long launch and their plans run under it (with g - 1 extra items only, half of the
-        # next group's plans started after the launch they should have hidden under: archive 165 -> 158 G, r06)
-        return P if g <= 1 else max(P + g - 1, 2 * g)
-    n_slots = 2 * lookahead(G_max)
+    P = _int_option(planners, "PAR_PLANNERS", 3, "planners / PAR_PLANNERS")
+    group = _int_option(group, "PAR_GROUP", None, "group / PAR_GROUP")      # (A/B sessions: 1 = the ungrouped launches of r05)
+    n_slots = _ring_slots(P, group)                      # constant for the whole call: free[k % n_slots] below relies on it
     main = torch.cuda.current_stream(dev)
     ring = _borrow_plan_ring(dev, n_slots, P)
     sides, work, aux, free = ring["sides"], ring["work"], ring["aux"], ring["free"]
 
     def plan_item(item, j, ready):
         slot, stream = j % n_slots, sides[j % P]
-        st_t, sp_t, sig_t = item[0], item[1], item[2]
-        if sig_t.ndim == 2:
-            len_in = sig_t.shape[0]
-        else:
-            len_in = item[4] if len(item) > 4 else sig_t.numel() // (item[3] if len(item) > 3 else 1)
         stream.wait_event(ready)                       # the item's tensors were produced on the main stream
         if free[slot] is not None:
             stream.wait_event(free[slot])              # the K_sinc that last read this slot is done
         # sizing reductions, (re)allocation and the plan itself all live on the side stream: a .item() there
         # does not wait for the K_sinc running on the main stream
         with torch.cuda.stream(stream):
-            plan = speed_plan_dev(st_t, sp_t, len_in, dev, fused=True, work=work[slot], aux=aux[slot], stream=stream)
+            plan = speed_plan_dev(item.st_t, item.sp_t, item.len_in, dev, fused=True, work=work[slot], aux=aux[slot],
+                                  stream=stream)
         # allocated (or regrown) under the side stream, read by the K_sinc on the main stream: without this a
         # block freed at generator teardown returns to the side stream's pool while that kernel still runs
         plan.work.record_stream(main)
@@ -372,9 +424,9 @@ def varispeed_batch_dev(items, NT, dev=None, planners=None, group=None):
         while True:
             # take items BEFORE launching the next K_sinc: whatever their producer enqueues on the main stream (uploads,
             # generators) then precedes the long kernel instead of queueing behind it
-            while not done and len(ahead) < lookahead(g_now):
+            while not done and len(ahead) < _lookahead(P, g_now):
                 try:
-                    item = next(it)
+                    item = work_item(next(it))
                 except StopIteration:
                     done = True
                     break
@@ -384,14 +436,10 @@ def varispeed_batch_dev(items, NT, dev=None, planners=None, group=None):
                 j += 1
             if not ahead:
                 return
-            head = ahead[0][1]
-            cls = _group_class(head)
-            g_now = 1 if cls is None else (int(group) if group is not None else _group_size(head))
-            if g_now > 1 and not done and len(ahead) < g_now:
-                continue                                   # (take the rest of the group first)
-            grp = [ahead.popleft()]
-            while len(grp) < g_now and ahead and _group_class(ahead[0][1]) == cls:
-                grp.append(ahead.popleft())
+            g_now, n = _next_group([item for _, item, _ in ahead], group, done)
+            grp = [ahead.popleft() for _ in range(n)]      # (none: take the rest of the group first)
+            if not grp:
+                continue
             plans = [fut.result() for _, _, fut in grp]
             if len(grp) > 1 and all(p.fused_ok for p in plans) and int(NT) == 32:
                 outs = _resample_group(plans, [g_item for _, g_item, _ in grp], NT, dev)
@@ -413,6 +461,29 @@ def varispeed_batch_dev(items, NT, dev=None, planners=None, group=None):
 _pinned_ring = {}
 
 
+def _pinned_view(ring, s, like, slack):
+    """View shaped like tensor `like` of slot s of a ring of pinned float32 buffers; a slot too small is regrown with `slack`."""
+    numel = like.numel()
+    if ring[s] is None or ring[s].numel() < numel:
+        ring[s] = torch.empty(int(numel * slack) + 4096, dtype=torch.float32).pin_memory()
+    return ring[s][:numel].view(like.shape)
+
+
+def _download_to_slot(out_t, ring, s, slack, main, down):
+    """The device-to-host hand-off: copy out_t (ready on `main`) into slot s of the pinned ring on the `down` stream.
+    -> (view of the slot shaped like out_t, event: the copy has landed)."""
+    view = _pinned_view(ring, s, out_t, slack)
+    done = torch.cuda.Event()
+    done.record(main)
+    down.wait_event(done)
+    with torch.cuda.stream(down):
+        view.copy_(out_t, non_blocking=True)
+        landed = torch.cuda.Event()
+        landed.record(down)
+    out_t.record_stream(down)
+    return view, landed
+
+
 def varispeed_batch_host(items, NT, dev=None):
     """Fused resampling of a batch of HOST-resident files on one GPU with the bus kept busy in both directions: the
     upload of file k+1 (its own stream) runs while file k's output is still going back (a third stream); plan and
@@ -430,15 +501,9 @@ def varispeed_batch_host(items, NT, dev=None):
     main = torch.cuda.current_stream(dev)
     up, down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
     pin_in, pin_out = _pinned_ring.setdefault(("in", dev), [None, None]), _pinned_ring.setdefault(("out", dev), [None, None])
-    in_done, out_done = [None, None], [None, None]      # events: upload from / download into the slot finished
+    in_done = [None, None]                               # events: the upload from the staging slot finished
     work = aux = None
-    pending = None                                       # (index, view of pin_out, event) of the previous file
-
-    def pinned(buf, numel):
-        if buf is None or buf.numel() < numel:
-            buf = torch.empty(int(numel * 1.05) + 4096, dtype=torch.float32).pin_memory()
-        return buf
-
+    pending = None                                       # (index, view of pin_out, event: landed) of the previous file
     for k, (st, sp, sig) in enumerate(items):
         slot = k % 2
         st = np.ascontiguousarray(st, dtype=np.float64)
@@ -452,8 +517,7 @@ def varispeed_batch_host(items, NT, dev=None):
         if not src.is_pinned():
             if in_done[slot] is not None:
                 in_done[slot].synchronize()              # the upload that last read this staging slot is through
-            pin_in[slot] = pinned(pin_in[slot], src.numel())
-            stage = pin_in[slot][:src.numel()].view(src.shape)
+            stage = _pinned_view(pin_in, slot, src, 1.05)
             _dev.host_copy(stage, src)                   # (on the staging threads: one core's memcpy was this loop's pace, r06)
             src = stage
         with torch.cuda.stream(up):
@@ -468,22 +532,13 @@ def varispeed_batch_host(items, NT, dev=None):
         plan = speed_plan_dev(st_t, sp_t, src.shape[0], dev, fused=True, max_out=max_out, work=work, aux=aux)
         work, aux = plan.work, plan.aux
         out_t = _resample_item(plan, (st_t, sp_t, sig_t), NT, dev)
-        done = torch.cuda.Event()
-        done.record(main)
         for t in (st_t, sp_t, sig_t):                    # allocated on `up`, read on `main`: the caching allocator must
             t.record_stream(main)                        # not recycle them under the kernels
-        pin_out[slot] = pinned(pin_out[slot], out_t.numel())     # slot of file k-2: the caller let go of it by advancing
-        view = pin_out[slot][:out_t.numel()].view(out_t.shape)
-        down.wait_event(done)
-        with torch.cuda.stream(down):
-            view.copy_(out_t, non_blocking=True)
-            out_done[slot] = torch.cuda.Event()
-            out_done[slot].record(down)
-        out_t.record_stream(down)
+        view, landed = _download_to_slot(out_t, pin_out, slot, 1.05, main, down)   # slot of file k-2: the caller let go of it
         if pending is not None:                          # hand out file k-1 while file k is on the device / the bus
             pending[2].synchronize()
             yield pending[0], pending[1]
-        pending = (k, view, out_done[slot])
+        pending = (k, view, landed)
     if pending is not None:
         pending[2].synchronize()
         yield pending[0], pending[1]
@@ -499,27 +554,13 @@ def varispeed_batch_gather(items, NT, dev=None, slots=3):
     Yields (index, host_view, plan) in order; host_view is a PINNED float32 CPU tensor shaped like the device output,
     valid until `slots - 1` more items have been taken (the ring wraps)."""
     dev = _dev.device_index(dev)
-    main = torch.cuda.current_stream(dev)
-    down = torch.cuda.Stream(device=dev)
-    ring = _pinned_ring.setdefault(("gather", dev), [None] * slots)
-    while len(ring) < slots:
-        ring.append(None)
-    landed = [None] * slots                              # event: the D2H into slot s is complete
-    pending = []                                         # (index, view, plan, event), oldest first
+    main, down = torch.cuda.current_stream(dev), torch.cuda.Stream(device=dev)
+    ring = _pinned_ring.setdefault(("gather", dev), [])
+    ring.extend([None] * (slots - len(ring)))
+    pending = []                                         # (index, view, plan, event: the D2H has landed), oldest first
     for k, out_t, plan in varispeed_batch_dev(items, NT, dev):
-        slot = k % slots
-        if ring[slot] is None or ring[slot].numel() < out_t.numel():
-            ring[slot] = torch.empty(int(out_t.numel() * 1.03) + 4096, dtype=torch.float32).pin_memory()
-        view = ring[slot][:out_t.numel()].view(out_t.shape)
-        done = torch.cuda.Event()
-        done.record(main)
-        down.wait_event(done)
-        with torch.cuda.stream(down):
-            view.copy_(out_t, non_blocking=True)
-            landed[slot] = torch.cuda.Event()
-            landed[slot].record(down)
-        out_t.record_stream(down)
-        pending.append((k, view, plan, landed[slot]))
+        view, landed = _download_to_slot(out_t, ring, k % slots, 1.03, main, down)
+        pending.append((k, view, plan, landed))
         if len(pending) >= slots - 1:                    # keep slots - 1 copies in flight behind the compute
             i, v, p, ev = pending.pop(0)
             ev.synchronize()
@@ -648,17 +689,6 @@ def sinc_core(sample_at, signal, lowpass, output, win_func, N):
 
 # ----------------------------------------------------------------------------- run
 
-class _Progress:
-    """Progress reporting with the reference's signal protocol: `prog_sig.notifyProgress.emit(value)`; silent
-    when no signal object was given."""
-
-    def __init__(self, prog_sig):
-        self._emit = prog_sig.notifyProgress.emit if prog_sig else (lambda value: None)
-
-    def __call__(self, value):
-        self._emit(value)
-
-
 def _plan_positions(sig_shape, sr, speed_curve, lag_curve, want_fused, dev):
     """(SpeedPlan or None, float64 position tensor or None) for one file.  Speed curve: the plan; its position
     array is only materialised when the fused K_sinc cannot be used.  Lag curve: K_lag positions."""
@@ -686,7 +716,7 @@ def run(filenames, signal_data=None, speed_curve=None, resampling_mode="Linear",
     channel, then 100 per file.  `signal_data` optionally supplies decoded `(signal, sr)` pairs.  The file's
     channels, its positions (or the fused plan) and the interleaved output stay in HBM; one D2H per file."""
     from . import io_ops
-    progress = _Progress(prog_sig)
+    progress = prog_sig.notifyProgress.emit if prog_sig else (lambda value: None)      # (the reference's signal protocol)
     progress(0)
     dev = _dev.device_index(None)
     decoded = signal_data if signal_data is not None else [None] * len(filenames)
@@ -703,26 +733,9 @@ def run(filenames, signal_data=None, speed_curve=None, resampling_mode="Linear",
             n_out_ch = len(use_channels)
             length = plan.len_out if pos_t is None else pos_t.numel()
             out_t = _dev.empty((length, n_out_ch), torch.float32, dev)
-            layout = dict(sig_stride=n_ch_in, len_in=n_in, out_stride=n_out_ch)
-            flat_in, flat_out = sig_t.reshape(-1), out_t.reshape(-1)                # strided channel views, no copies
-            k = 0
-            while k < n_out_ch:
-                ch = use_channels[k]
-                if resampling_mode == "Sinc" and pos_t is None and k + 1 < n_out_ch:
-                    # two channels per launch: they share the positions, hence the whole weight computation
-                    varispeed_fused_stereo_dev(plan, flat_in[ch:], flat_in[use_channels[k + 1]:], sinc_quality,
-                                               flat_out[k:], flat_out[k + 1:], **layout)
-                    progress((k + 1) / n_out_ch * 100)
-                    k += 1
-                elif resampling_mode == "Sinc":
-                    if pos_t is None:
-                        varispeed_fused_dev(plan, flat_in[ch:], sinc_quality, flat_out[k:], **layout)
-                    else:
-                        sinc_resample_dev(pos_t, flat_in[ch:], sinc_quality, flat_out[k:], dev=dev, **layout)
-                elif resampling_mode == "Linear":
-                    linear_resample_dev(pos_t, flat_in[ch:], flat_out[k:], dev=dev, **layout)
-                progress((k + 1) / n_out_ch * 100)
-                k += 1
+            resample_channels(sig_t.reshape(-1), out_t.reshape(-1), list(zip(use_channels, range(n_out_ch))),
+                              dict(sig_stride=n_ch_in, len_in=n_in, out_stride=n_out_ch), sinc_quality, resampling_mode,
+                              plan, pos_t, progress)
             # pinned staging for the one D2H of the file (4x the pageable rate, tools/bench_e2e.py)
             host = torch.empty(out_t.shape, dtype=torch.float32, pin_memory=True)
             host.copy_(out_t)

@@ -536,9 +536,24 @@ def test_run_writes_res_wav_like_reference(par, golden, tmp_path):
     assert sr2 == sr and ch == 1 and y.shape == (len(gp["bench_pos"]), 1)
     assert relerr(y[:, 0], g["bench_y"]) < TOL
     assert seen[0] == 0 and seen[-1] == 100 and 100.0 in seen
-    par.resampling.run((fn,), signal_data=((sig, sr),), speed_curve=curve, resampling_mode="Linear")
+    assert seen == [0, 100.0, 100]
+    # progress: 0, then (k + 1) / channels * 100 after every channel -- a stereo launch reports both of its channels --, then 100
+    del seen[:]
+    par.resampling.run((fn,), signal_data=((sig, sr),), speed_curve=curve, resampling_mode="Sinc", sinc_quality=32, prog_sig=Sig)
+    y, _, ch = io_ops.read_file(str(tmp_path / "tape_res.wav"))
+    assert ch == 2 and relerr(y[:, 0], g["bench_y"]) < TOL
+    assert seen == [0, 50.0, 100.0, 100]
+    del seen[:]
+    sig3 = np.concatenate((sig, sig[:, :1]), axis=-1)                # two channels in one launch, the third on its own
+    par.resampling.run((fn,), signal_data=((sig3, sr),), speed_curve=curve, resampling_mode="Sinc", sinc_quality=32, prog_sig=Sig)
+    y, _, ch = io_ops.read_file(str(tmp_path / "tape_res.wav"))
+    assert ch == 3 and relerr(y[:, 0], g["bench_y"]) < TOL and relerr(y[:, 2], g["bench_y"]) < TOL
+    assert seen == pytest.approx([0, 100 / 3, 200 / 3, 100.0, 100])
+    del seen[:]
+    par.resampling.run((fn,), signal_data=((sig, sr),), speed_curve=curve, resampling_mode="Linear", prog_sig=Sig)
     y, _, ch = io_ops.read_file(str(tmp_path / "tape_res.wav"))
     assert ch == 2 and relerr(y[:, 0], np.interp(gp["bench_pos"], np.arange(96000), sig[:, 0], left=0, right=0)) < 1e-6
+    assert seen == [0, 50.0, 100.0, 100]
 
 
 # --------------------------------------------------------------------------------- filters
@@ -1612,6 +1627,41 @@ def test_batch_pipeline_equals_item_by_item(par):
     R.release_plan_rings()
     got = [out.clone() for _, out, _ in R.varispeed_batch_dev(items, 16)]
     assert all(t.equal(o, w) for o, w in zip(got, want))
+
+
+def test_plan_ring_wraps_and_holds_the_slots_the_call_can_use(par):
+    """The batch driver's cached plan ring has _ring_slots(planners, group) slots -- 16 for a default call, 32 with group=8 -- and
+    a batch longer than the ring (slots are planned again, their buffers grow and are reused: files below and above the
+    streaming kernel's 4-tile threshold alternate) gives bit for bit what planning and resampling item by item gives."""
+    t = par.torch
+    R = par.resampling
+    R.release_plan_rings()
+    rng = np.random.default_rng(36)
+    items = []
+    for i in range(36):
+        n = (5_000, 70_000)[i % 2]
+        m = max(3, n // 256)
+        sp = 1.0 + 0.05 * np.sin(np.arange(m) * 0.37 + i) + 0.001 * rng.standard_normal(m)
+        items.append((t.from_numpy(np.linspace(0, n, m)).cuda(), t.from_numpy(sp).cuda(), t.from_numpy(inputs.noise(n, 300 + i)).cuda()))
+    want = []
+    for st_t, sp_t, sig_t in items:
+        plan = R.speed_plan_dev(st_t, sp_t, sig_t.numel(), fused=True)
+        assert plan.fused_ok
+        want.append(R.varispeed_fused_dev(plan, sig_t, 32).clone())
+
+    def slots():
+        ring = R._plan_rings.get(t.cuda.current_device())           # (allocated work / aux buffers and slot events)
+        return None if ring is None else [sum(x is not None for x in ring[key]) for key in ("work", "aux", "free")]
+
+    for kwargs, n_slots in (({}, 16), ({"group": 8}, 32)):
+        got = [(k, out.clone()) for k, out, _ in R.varispeed_batch_dev(items, 32, **kwargs)]
+        t.cuda.synchronize()
+        assert [k for k, _ in got] == list(range(36))
+        for (k, out), w in zip(got, want):
+            assert out.shape == w.shape and t.equal(out, w), (kwargs, k)
+        assert slots() == [n_slots] * 3, kwargs
+    R.release_plan_rings()
+    assert slots() is None
 
 
 def test_degenerate_segment_behind_the_trim_is_harmless(par):
