@@ -228,21 +228,22 @@ __device__ __forceinline__ S2Row s2_place_row(const uint4 ra, const uint4 rb, co
 // s_waitcnt vmcnt(5) (everything but the previous iteration's five memory operations has landed), no branch in the body.
 // The ring holds 8 chunks of float32 samples (near taps) and 4 of the float16 images; the bank is single-buffered (an
 // iteration's gathers precede its bank writes in program order, LDS serves a wave's operations in order).
-// Order of one iteration of the MONO loop at two waves per SIMD, as built with -DPAR_S3_EARLY_LDS=1 (k_sinc_pipe<1, 2>; the default, 0,
-// is the r06 order above: the new one becomes the default once its A/B against it is on record, NOTES).
-// At four waves a wave that waits for its own LDS read is covered by the other three; at two it is not, so every read is
-// issued a stage ahead of its use:
+// Order of one iteration of the MONO loop at two waves per SIMD (k_sinc_pipe<1, 2>, r08; the fc = 1 kernel <1, 1> at four waves, the
+// one-channel kernel <2, 3> and the stereo loop keep the order above).  At four waves a wave that waits for its own LDS read is
+// covered by the other three; at two it is not, so every read is issued a stage ahead of its use:
 //     wait vmcnt + fence
 //     READS    the records of PLACE(k + 1), CONV's ring chunk, the gathers of OUT(k) (3 rows + 5 ring samples per output):
 //              their addresses are loop state, the data landed before the fence
 //     PLACE(k + 1) behind a partial lgkmcnt (the records alone); the loop's exit test (scalar) rides beside it
 //     READS    BANK(k + 1)'s six image fragments, as soon as ws is known
-//     OUT(k)   arithmetic, pinned here: the fragments land under it
-//     BANK(k + 1) MFMAs, row writes (behind OUT(k)'s gathers); CONV arithmetic + image writes (behind the fragment reads)
+//     OUT(k)   arithmetic, pinned here: the fragments land under it -- both rows in the fc = 1 and the order-6 loop; in the
+//              order-5 loop (the benchmark's fc < 1 passes) the first row only
+//     BANK(k + 1) MFMAs -- order 5: OUT(k)'s second row dealt out behind them, two vector instructions to an MFMA (which hides
+//              that many) -- then the row writes (behind OUT(k)'s gathers); CONV arithmetic + image writes (behind the
+//              fragment reads)
 //     FETCH, DMA, stores, fence
 // Same hazards as above -- nothing read that the iteration wrote, gathers before row writes, fragment reads before image writes,
-// one fence, one vmcnt wait -- and the same arithmetic expressions.  (Whether the outputs are bit-identical to the r06 order's --
-// the compiler contracts multiplies and adds across statements, and the block structure moved -- is for a dump comparison to show.)
+// one fence, one vmcnt wait -- and the same arithmetic expressions: the outputs are bit-identical to the r06 order's (NOTES r08).
 // (tools/isa_census.py --waits lists each read, the wait that covers it and the wave's own vector work in between.)
 // Whatever is not the plain case -- the first pass of a run, a pass that meets a flagged tile or block, the end of the
 // wave's range, a change of tap regime, a conversion window that has drifted out of its slack -- leaves the loop
@@ -524,9 +525,6 @@ constexpr float kEpMom5 = 0.0105f / (1.0f - 0.0105f), kEpMom5Lo = 0.95f * kEpMom
 #ifndef PAR_S3_PIN_MONO
 #define PAR_S3_PIN_MONO 0       // 1: the mono loop's row results pinned like the stereo loop's (234 instead of 250 registers, 1 % slower)
 #endif
-#ifndef PAR_S3_EARLY_LDS
-#define PAR_S3_EARLY_LDS 0      // the mono loop's LDS reads issued a stage ahead of their use (see the loop): 0 = the r06 order, 1 = the
-#endif                          // fc < 1 kernel <1, 2>, 3 = the fc = 1 kernel <1, 1> as well.  0 until the A/B on the GPU is on record (NOTES)
 // KIND: which streams of the launch the kernel takes, and what it has to know for them (r06).  A wave issues an instruction
 // every ~5 cycles whatever its kind, so two waves per SIMD -- what the 25 constant fragments of both filter sets leave room
 // for -- cannot fill the SIMD's issue slots; a stream whose tiles hold fc = 1 outputs only needs the fc = 1 bank's ten:
@@ -549,8 +547,8 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
   constexpr bool kPick = KIND == 3;               // one channel of two-channel frames: stereo ring, mono loop
   constexpr bool kTwo = NCH == 2 && !kPick;       // both channels of a pass: the stereo loop
   constexpr bool kMom = KIND != 1;
-  // the mono loop with its LDS reads a stage ahead (PAR_S3_EARLY_LDS)
-  constexpr bool kEarly = NCH == 1 && ((KIND == 2 && (PAR_S3_EARLY_LDS & 1)) || (KIND == 1 && (PAR_S3_EARLY_LDS & 2) == 2));
+  // the mono loop at two waves per SIMD: its LDS reads a stage ahead (see the loop)
+  constexpr bool kEarly = NCH == 1 && KIND == 2;
   const int l = threadIdx.x & (kWave - 1);
   if (bx < a.n_edge) {                            // an end tile's wave: tile 0, then n_full - 2, n_full - 1 and the partial one
     if constexpr (KIND == 1) return;              // (done by the launch of the other kind)
@@ -1008,16 +1006,38 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         __builtin_amdgcn_sched_barrier(0);
         // ... and OUT(P)'s arithmetic runs while they are on their way.  (Pinned: left alone the compiler sinks a row's arithmetic
         // into its store's lane mask at the END of the iteration, as in the stereo loop.)
+        if constexpr (MODE == 2) {
+          // Order 5: OUT(P)'s first row in the fragments' shadow, its second row left to the matrix work -- an MFMA hides two
+          // vector instructions behind it, so the row is dealt out two to an MFMA for as long as it lasts.  (Not the
+          // order-6 loop: with 31 MFMAs and nine accumulators live the scheduler does not take the pipeline and leaves the whole
+          // row behind the first MFMA.  Not the fc = 1 loop: its rows are short, and with one of them gone the first fragment
+          // is waited for 84 priced cycles after its read instead of 167; measured, the step is the same either way, NOTES r08.)
+          res[0] = s3_out_math<MODE>(G[0], P.s[0], P.ep[0]);
+          asm volatile("" : "+v"(res[0]));
+          // (order 5 leaves m6 of the gathered rows unread: kept alive to here, or its register is handed out again under
+          // PLACE and the write to it waits for the LAST gather)
+          asm volatile("" ::"v"(G[0].Mh[3]));
+          __builtin_amdgcn_sched_barrier(0);
+          // the matrix work and the row writes (behind OUT(P)'s gathers)
+          res[1] = s3_out_math<MODE>(G[1], P.s[1], P.ep[1]);
+          bank_math<true, false>(L, fr, fmr, X, l);
+          asm volatile("" : "+v"(res[1]));
+          asm volatile("" ::"v"(G[1].Mh[3]));
 #pragma unroll
-        for (int r = 0; r < 2; ++r) res[r] = s3_out_math<MODE>(G[r], P.s[r], P.ep[r]);
-        asm volatile("" : "+v"(res[0]), "+v"(res[1]));
-        // (order 5 leaves m6 of the gathered rows unread: kept alive to here, or its register is handed out again under
-        // PLACE and the write to it waits for the LAST gather)
-        if constexpr (MODE == 2) asm volatile("" ::"v"(G[0].Mh[3]), "v"(G[1].Mh[3]));
-        __builtin_amdgcn_sched_barrier(0);
-        // the matrix work and the row writes (behind OUT(P)'s gathers), CONV's arithmetic and image writes (behind the fragment
-        // reads), then FETCH and the stores: five memory operations, in this order
-        bank_math<MODE != 1, MODE == 3>(L, fr, fmr, X, l);
+          for (int i = 0; i < 28; ++i) {                            // (the bank's 13 + 15 MFMAs)
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // two VALU
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 2; ++r) res[r] = s3_out_math<MODE>(G[r], P.s[r], P.ep[r]);
+          asm volatile("" : "+v"(res[0]), "+v"(res[1]));
+          __builtin_amdgcn_sched_barrier(0);
+          // the matrix work and the row writes (behind OUT(P)'s gathers)
+          bank_math<MODE != 1, MODE == 3>(L, fr, fmr, X, l);
+        }
+        // CONV's arithmetic and image writes (behind the fragment reads), then FETCH and the stores: five memory operations, in
+        // this order
         // (the loop's exit test is ~35 scalar instructions; left alone they all sink behind the stores, where the wave offers
         // the vector port nothing: worked out here, beside the matrix work)
         int oki = __builtin_amdgcn_readfirstlane((int)ok);

@@ -2,7 +2,8 @@
 """Per-stage instruction census of the streaming kernel's two hot loops (fc = 1 and fc < 1), from the compiler's listing.
     python tools/isa_census.py [NCH [KIND]] [extra hipcc flags]   -> prints the table committed as profiles/r06_isa_census.txt
     python tools/isa_census.py --waits [NCH [KIND]] [flags]       -> per hot loop, every LDS read with the first s_waitcnt lgkmcnt
-                                                                     that covers it and the wave's own vector work in between
+                                                                     that covers it and the wave's own vector work in between,
+                                                                     and the instruction pattern of the loop's MFMA stretch
 Every instruction between a loop's `s_waitcnt vmcnt(N)` head and its back edge is attributed to the STAGE its .loc source
 line belongs to (source ranges of sinc2.hip named below; inlined header code is charged to the last csrc line seen)."""
 import os, re, subprocess, sys, tempfile
@@ -103,6 +104,20 @@ def waits_table(L, h, back, files, stages):
     for ln, txt, st, wl, n, nv, pc in rows:
         print(f"{ln:7d}  {txt:26s} {st:10s} " + (f"{wl:8d} {n:7d}" if wl else f"{'(next it.)':>8s} {'':>6s}") + f" {nv:13d} {pc:11.0f}")
 
+def mfma_stretch(L, h, back):
+    """--waits: the loop body from its first to its last MFMA as one letter per instruction (M MFMA, v other vector, d LDS,
+    s scalar, w s_waitcnt, n s_nop): shows what the wave's own vector work the scheduler has laid behind each MFMA (an MFMA
+    hides two) -- OUT's second row in the order-5 loop of k_sinc_pipe<1, 2>."""
+    idx = [i for i in range(h, back + 1) if L[i].strip().startswith("v_mfma")]
+    seq = ""
+    for i in range(idx[0], idx[-1] + 1):
+        l = L[i].strip()
+        if not l or l.startswith((";", ".", "//")) or l.endswith(":"): continue
+        op = l.split()[0]
+        seq += ("M" if op.startswith("v_mfma") else "v" if op.startswith("v_") else "d" if op.startswith("ds_") else
+                "w" if op == "s_waitcnt" else "n" if op == "s_nop" else "s")
+    return len(idx), seq
+
 def compile_listing(extra=()):
     """sinc2.hip's gfx950 listing with the project's flags (+ line tables): (lines, {file number: name}, stage table)"""
     tmp = tempfile.mkdtemp()
@@ -156,6 +171,10 @@ def main():
             print(f"\nloop {hi} ({what}): listing lines {h}..{back}, heads (s_waitcnt vmcnt) in the body: "
                   f"{sum(1 for i in range(h, back + 1) if re.search(r's_waitcnt.*vmcnt', L[i]))}")
             waits_table(L, h, back, files, stages)
+            n, seq = mfma_stretch(L, h, back)
+            behind = [len(g) for g in "".join(c for c in seq if c in "Mv").split("M")[1:-1]]
+            print(f"matrix stretch: {n} MFMAs, {seq.count('v')} vector instructions between the first and the last, "
+                  f"{sum(1 for b in behind if b >= 2)} MFMAs with two or more behind them\n  {seq}")
             continue
         cur, last_stage = ("?", 0), "loop"
         tab = {}
