@@ -117,7 +117,8 @@ int par_copy_segments_f32(int device, const float* src, int64_t src_stride, int6
  *   spec     device complex64 [n_frames][bins], frame-major (par_stft_f32 output); read only
  *   gain_db  device f32 [n_frames][bins], zero-initialised by the caller; updated with an atomic max, which
  *            equals the reference's marker-by-marker clip because the mask is non-negative (heal.hip header)
- * A marker whose box or surrounding frames leave the spectrogram contributes nothing. */
+ * A marker whose box or surrounding frames leave the spectrogram contributes nothing.  A NaN gain (a NaN in a surrounding
+ * frame, or Inf * 0 at the box's end) stays NaN like np.clip's, whatever other markers cover the bin. */
 int par_inpaint_gain_db_c64(int device, const float* spec, int64_t n_frames, int64_t bins, const int32_t* markers,
                             int64_t n_markers, float* gain_db, void* stream);
 

@@ -70,10 +70,13 @@ __global__ void __launch_bounds__(256) k_inpaint_gain(const float2* __restrict__
     // x_i = linspace(frame_b, frame_a, nf)[i]; normalised distance on the 2-point frame grid
     const double tt = nf > 1 ? (double)i / (double)(nf - 1) : 0.0;
     const double target = before * (1.0 - tt) + after * tt;
-    double g = target - spec_db(col[(frame_b + i) * bins]);
-    g = g < 255.0 ? g : 255.0;
-    const float gf = (float)g;
-    if (gf > 0.0f) atomicMax(reinterpret_cast<int*>(gain + (frame_b + i) * bins + b0 + bi), __float_as_int(gf));
+    const double g = target - spec_db(col[(frame_b + i) * bins]);
+    // np.clip(g, previous, 255) keeps a NaN (a NaN or Inf in the surrounding frames: db_math.h), so the clip does too; rounding is
+    // monotone and 255 a float, so clipping after the conversion gives what clipping before it gave
+    float gf = (float)g;
+    gf = gf > 255.0f ? 255.0f : gf;
+    // a NaN goes in with its sign bit cleared: as an integer a positive NaN beats every finite gain and +Inf, in either marker order
+    if (!(gf <= 0.0f)) atomicMax(reinterpret_cast<int*>(gain + (frame_b + i) * bins + b0 + bi), __float_as_int(gf) & 0x7fffffff);
   }
 }
 
