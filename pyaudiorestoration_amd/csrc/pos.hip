@@ -175,16 +175,6 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_apply(typename Op::T* __r
   }
 }
 
-template <typename Op>
-static int inclusive_scan(typename Op::T* data, int64_t n, typename Op::T* bsum, hipStream_t s) {
-  const int64_t nb = ceil_div(n, kScanTile);
-  hipLaunchKernelGGL(k_scan_reduce<Op>, dim3((unsigned)nb), dim3(kScanThreads), 0, s, data, n, bsum);
-  hipLaunchKernelGGL(k_scan_top<Op>, dim3(1), dim3(kScanThreads), 0, s, bsum, nb);
-  hipLaunchKernelGGL(k_scan_apply<Op>, dim3((unsigned)nb), dim3(kScanThreads), 0, s, data, n, bsum);
-  PAR_HIP_CHECK(hipGetLastError());
-  return PAR_OK;
-}
-
 // ------------------------------------------------------------------------- stage kernels
 __global__ void k_init_header(PlanHeader* h, int64_t m, int lazy) {
   h->m = m;
@@ -203,30 +193,11 @@ __global__ void k_init_header(PlanHeader* h, int64_t m, int lazy) {
   h->speed_sum = 0.0;
   h->ck_len = 0;
   h->ck_valid = 0;
-  h->pad2 = 0;
+  h->done_off_apply_trim = 0;
   h->n_long = 0;
-  h->pad3 = 0;
+  h->done_tile_seg_publish = 0;
   h->written = 0;
   h->first_bad = kNoTrim;
-}
-
-// a_i (util/resampling.py:103,:111) in numpy's order, converted EXACTLY to 64.64 fixed point.
-__global__ void k_seg_want(const double* __restrict__ st, const double* __restrict__ sp, int64_t nseg,
-                           U128* __restrict__ a_fix, PlanHeader* __restrict__ h) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nseg) return;
-  const double period = st[i + 1] - st[i];
-  const double mean = (sp[i] + sp[i + 1]) / 2.0;
-  const double a = period * mean;
-  U128 e{0ull, 0ull};
-  if (!(a >= 0x1p-11 && a < 0x1p62)) {
-    atomicOr(&h->flags, kFlagRange);
-  } else {
-    const double ip = floor(a);
-    e.hi = (unsigned long long)ip;
-    e.lo = (unsigned long long)((a - ip) * 0x1p64);     // exact: < 2^64, at most 64 fractional bits
-  }
-  a_fix[i] = e;
 }
 
 __device__ __forceinline__ unsigned long long round_fixed(U128 A, bool* ambiguous) {
@@ -236,32 +207,11 @@ __device__ __forceinline__ unsigned long long round_fixed(U128 A, bool* ambiguou
   return A.hi + (A.lo > half ? 1ull : 0ull);
 }
 
-// n_i = round(A_i) - round(A_{i-1});  seg_start[i] = round(A_{i-1})
-__global__ void k_seg_lengths(const U128* __restrict__ A, int64_t nseg, int64_t* __restrict__ seg_start,
-                              PlanHeader* __restrict__ h) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nseg) return;
-  bool amb = false;
-  const unsigned long long Ni = round_fixed(A[i], &amb);
-  const unsigned long long Np = i > 0 ? round_fixed(A[i - 1], &amb) : 0ull;
-  seg_start[i] = (int64_t)Np;
-  if (i == nseg - 1) {
-    seg_start[nseg] = (int64_t)Ni;
-    h->total_written = (int64_t)Ni;
-  }
-  int f = 0;
-  if (amb) f |= kFlagAmbiguous;
-  // n_i < 2: the reference divides by zero / indexes an empty array -- if it ever gets there.  Downstream the segment
-  // counts as empty (S_i = 0, cannot straddle n_in); k_trim raises the flag unless the trim fires in front of it.
-  if (Ni < Np + 2ull) atomicMin(&h->first_bad, (unsigned long long)i);
-  if (f) atomicOr(&h->flags, f);
-}
-
 // sum(speeds) for the reference's buffer bound int(mean(speeds) * span * 1.01) (:108).  numpy sums pairwise; any other
 // order may differ in the last bits, so this sum is made ACCURATE instead (compensated per thread, tree across lanes,
 // compensated + tree again over the per-wave partials in the last workgroup: <= ~18 ulp-roundings, 2e-15 relative)
-// and k_trim sends the plan to the serial path -- which restates numpy's order -- in the rare case where that
-// uncertainty could move int().
+// and trim_body sends the plan to the serial path -- which restates numpy's order -- in the rare case where that
+// uncertainty could move int().  (The go with host-made lengths; otherwise the sum rides in k_len_reduce / k_len_top.)
 __global__ void __launch_bounds__(256) k_speed_sum(const double* __restrict__ sp, int64_t m, double* __restrict__ partial,
                                                    PlanHeader* __restrict__ h) {
   __shared__ double red[256];
@@ -279,7 +229,7 @@ __global__ void __launch_bounds__(256) k_speed_sum(const double* __restrict__ sp
   if ((threadIdx.x & (kWave - 1)) == 0) partial[blockIdx.x * waves + threadIdx.x / kWave] = s;
   __threadfence();
   __syncthreads();
-  if (threadIdx.x == 0) is_last = atomicAdd(&h->pad2, 1) == (int)gridDim.x - 1;
+  if (threadIdx.x == 0) is_last = atomicAdd(&h->done_off_apply_trim, 1) == (int)gridDim.x - 1;   // borrowed: see the reset below
   __syncthreads();
   if (!is_last) return;
   __threadfence();
@@ -300,7 +250,7 @@ __global__ void __launch_bounds__(256) k_speed_sum(const double* __restrict__ sp
   }
   if (threadIdx.x == 0) {
     h->speed_sum = red[0];
-    h->pad2 = 0;                                 // the counter serves k_off_apply_trim next
+    h->done_off_apply_trim = 0;                  // the counter serves k_off_apply_trim next
   }
 }
 
@@ -371,7 +321,7 @@ __global__ __launch_bounds__(64) PLAN_VGPR_CAP void k_seg_sum(const double* __re
         if (count_long) {
           atomicAdd(&h->n_long, 1);
           S[i] = 0.0;
-          // first go of a sparse curve (mode 1): the plan is made again with the chunked cumsum, so the rest of THIS pass is void --
+          // first go of a sparse curve (count_long 1): the plan is made again with the chunked cumsum, so the rest of THIS pass is void --
           // the kernels behind see the mark and leave at once instead of scanning undefined sums
           if (count_long == 1) atomicOr(&h->lazy_fail, 4);
         }
@@ -1057,9 +1007,8 @@ __device__ __forceinline__ void tile_entry(const double* __restrict__ sp, const 
 __device__ __forceinline__ void tile_seg_body(const double* __restrict__ sp, const int64_t* __restrict__ seg_start,
                            const double* __restrict__ seg_off, int64_t nseg, const double* __restrict__ ck, int64_t ck_len,
                            int64_t max_tiles, int64_t* __restrict__ tile_seg, SegFast* __restrict__ seg_fast,
-                           long long* __restrict__ tile_st, TileHdr* __restrict__ hdr, PlanHeader* __restrict__ h, const int64_t x,
-                           const bool lazy = false) {
-  const long long len_out = h->len_out;                // written by k_trim / the host path earlier on this stream
+                           long long* __restrict__ tile_st, TileHdr* __restrict__ hdr, PlanHeader* __restrict__ h, const int64_t x) {
+  const long long len_out = h->len_out;                // written by trim_body / the host path earlier on this stream
   const long long n_tiles = (len_out + kSincTileOutputs - 1) / kSincTileOutputs;
   if (n_tiles + 1 > max_tiles) {
     if (x == 0 && len_out > 0) atomicOr(&h->flags, kFlagCkOverflow);
@@ -1067,7 +1016,7 @@ __device__ __forceinline__ void tile_seg_body(const double* __restrict__ sp, con
   }
   if (x < nseg) {
     const long long a = seg_start[x], b = seg_start[x + 1];
-    if (!lazy && b > a && a < len_out && ck_slot0(a, x) + (b - a + kCk - 1) / kCk > ck_len)
+    if (b > a && a < len_out && ck_slot0(a, x) + (b - a + kCk - 1) / kCk > ck_len)
       atomicOr(&h->flags, kFlagCkOverflow);             // a needed segment has no checkpoints: fused path refused
     seg_fast[x] = seg_fast_record(sp, seg_off, x, b - a);
   }
@@ -1079,7 +1028,7 @@ __device__ __forceinline__ void tile_seg_body(const double* __restrict__ sp, con
     const long long mid = (lo + hi + 1) >> 1;
     if (seg_start[mid] <= sample) lo = mid; else hi = mid - 1;
   }
-  if (lo < nseg) tile_entry(sp, seg_start, seg_off, nseg, ck, ck_len, tile_seg, tile_st, hdr, x, n_tiles, sample, lo, lazy);
+  if (lo < nseg) tile_entry(sp, seg_start, seg_off, nseg, ck, ck_len, tile_seg, tile_st, hdr, x, n_tiles, sample, lo, false);
 }
 
 __global__ void k_tile_seg(const double* __restrict__ sp, const int64_t* __restrict__ seg_start,
@@ -1095,22 +1044,21 @@ __global__ void k_tile_seg_publish(const double* __restrict__ sp, const int64_t*
                                    const double* __restrict__ seg_off, int64_t nseg, const double* __restrict__ ck, int64_t ck_len,
                                    int64_t max_tiles, int64_t* __restrict__ tile_seg, SegFast* __restrict__ seg_fast,
                                    long long* __restrict__ tile_st, TileHdr* __restrict__ hdr, PlanHeader* __restrict__ h,
-                                   int64_t n_items, int lazy) {
+                                   int64_t n_items) {
   __shared__ int is_last;
-  if (h->lazy_fail) return;                             // the plan is being made again (eager, or with the chunked cumsum)
+  if (h->lazy_fail) return;                             // the plan is being made again (with the chunked cumsum)
   for (int64_t x0 = (int64_t)blockIdx.x * blockDim.x; x0 < n_items; x0 += (int64_t)gridDim.x * blockDim.x)
-    tile_seg_body(sp, seg_start, seg_off, nseg, ck, ck_len, max_tiles, tile_seg, seg_fast, tile_st, hdr, h, x0 + threadIdx.x,
-                  lazy != 0);
+    tile_seg_body(sp, seg_start, seg_off, nseg, ck, ck_len, max_tiles, tile_seg, seg_fast, tile_st, hdr, h, x0 + threadIdx.x);
   __threadfence();
   __syncthreads();
-  if (threadIdx.x == 0) is_last = atomicAdd(&h->pad3, 1) == (int)gridDim.x - 1;
+  if (threadIdx.x == 0) is_last = atomicAdd(&h->done_tile_seg_publish, 1) == (int)gridDim.x - 1;
   __syncthreads();
   if (!is_last || threadIdx.x != 0) return;
   __threadfence();
-  h->pad3 = 0;
+  h->done_tile_seg_publish = 0;
   const int fl = __hip_atomic_load(&h->flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   h->ck_len = ck_len;
-  h->ck_valid = (fl & ~kFlagCapAmbiguous) ? 0 : (lazy ? 2 : 1);     // 2: K_sinc may run, but there are no checkpoints to fill from
+  h->ck_valid = (fl & ~kFlagCapAmbiguous) ? 0 : 1;      // (a lazy plan's 2 is published by k_trim_lazy)
   h->flags = fl & ~kFlagCkOverflow;
 }
 
@@ -1505,42 +1453,6 @@ __device__ __forceinline__ void mark_direct(long long i, long long* direct, Plan
   else atomicOr(&h->flags, kFlagDirectOverflow);
 }
 
-// xs[i] = inclusive plain-f64 scan of S  ->  approx offsets xa_i = st0 + xs[i-1].
-// Build the parity-translation element of step i (x_i -> x_{i+1}) or mark it direct.
-__global__ void k_off_prepare(const double* __restrict__ S, const double* __restrict__ xs, const double* __restrict__ st,
-                              int64_t nseg, PElem* __restrict__ el, long long* __restrict__ direct,
-                              PlanHeader* __restrict__ h) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nseg) return;
-  const double st0 = st[0];
-  const double xa = st0 + (i > 0 ? xs[i - 1] : 0.0);
-  const double xb = st0 + xs[i];
-  const double lo = 1.0 - 0x1p-30, hi = 1.0 + 0x1p-30;
-  const int e = f64_exponent(xa);
-  bool interior = xa > 0.0 && S[i] > 0.0 && e > 64 && e < 2046 && f64_exponent(xa * lo) == e &&
-                  f64_exponent(xa * hi) == e && f64_exponent(xb * lo) == e && f64_exponent(xb * hi) == e;
-  PElem p{0, 0, 0, 0};
-  if (interior) {
-    // u = ulp in binade e = 2^(e-1075); S/u is an exact power-of-two scaling
-    const double t = ldexp(S[i], 1075 - e);
-    if (t < 0x1p62) {
-      const double fl = floor(t);
-      const long long q = (long long)fl;
-      const double fr = t - fl;                // exact
-      if (fr > 0.5) p.c0 = p.c1 = q + 1;
-      else if (fr < 0.5) p.c0 = p.c1 = q;
-      else {                                   // exact half: ties-to-even on the SUM's parity
-        p.c0 = q + (q & 1);
-        p.c1 = q + ((q + 1) & 1);
-      }
-    } else {
-      interior = false;
-    }
-  }
-  if (!interior) mark_direct(i, direct, h);
-  el[i] = p;
-}
-
 // head flags: a run starts at 0 and after every direct step
 __global__ void k_off_heads(PElem* __restrict__ el, int64_t nseg, const long long* __restrict__ direct,
                             const PlanHeader* __restrict__ h) {
@@ -1600,12 +1512,12 @@ __global__ void k_off_stitch(const double* __restrict__ S, const PElem* __restri
   h->n_runs = r;
 }
 
-// ---- fused stages of the device plan (r04) ----------------------------------------------------------------------------
-// Until r03 the plan was ~27 launches: every elementwise stage its own kernel around three-kernel scans, and a read-back
-// in the middle.  The elementwise stages now ride inside the scans' own passes (a block's reduce pass only needs the
-// block's elements, its apply pass has the running prefix at hand), single-thread epilogues run in the last block to
-// finish, and the read-back of the long-segment count is gone (a plan that turns out to hold long segments is simply made
-// again with the chunked-cumsum kernels in: sparse curves only, a few hundred segments).  Same arithmetic, bit for bit.
+// ---- fused stages of the device plan ----------------------------------------------------------------------------------
+// The elementwise stages ride inside the scans' own passes (a block's reduce pass only needs the block's elements, its
+// apply pass has the running prefix at hand) and single-thread epilogues run in the last block to finish.
+//
+// a_i (util/resampling.py:103,:111) in numpy's order, converted EXACTLY to 64.64 fixed point: scanned in any association,
+// the running sum is still the one exact sum (header comment, chain (1)).
 __device__ __forceinline__ U128 want_fixed(const double* __restrict__ st, const double* __restrict__ sp, int64_t i, bool* bad) {
   const double period = st[i + 1] - st[i];
   const double mean = (sp[i] + sp[i + 1]) / 2.0;
@@ -1621,9 +1533,9 @@ __device__ __forceinline__ U128 want_fixed(const double* __restrict__ st, const 
   return e;
 }
 
-// lengths, pass 1: a_i in 64.64 fixed point on the fly, block sums; the header is initialised here by block 0 before any
-// flag can be raised?  No: flags are raised by any block, so the header is initialised by k_init_header in front.
-// Also the per-wave partial sums of the speed samples for the reference's buffer bound (k_speed_sum's role).
+// lengths, pass 1: a_i in 64.64 fixed point on the fly, block sums (any block may raise a flag, so the header is initialised
+// by k_init_header in front, not here).  Also the per-wave partial sums of the speed samples for the reference's buffer
+// bound (k_speed_sum's role, and its reason for compensating them).
 __global__ __launch_bounds__(kScanThreads) void k_len_reduce(const double* __restrict__ st, const double* __restrict__ sp,
                                                               int64_t nseg, U128* __restrict__ bsum, double* __restrict__ partial,
                                                               PlanHeader* __restrict__ h) {
@@ -1691,7 +1603,7 @@ __global__ __launch_bounds__(kScanThreads) void k_len_top(U128* __restrict__ bsu
   if (threadIdx.x == 0) h->speed_sum = red[0];
 }
 
-// lengths, pass 3: the running 64.64 sum at every segment -> n_i = round(A_i) - round(A_{i-1}), seg_start (k_seg_lengths)
+// lengths, pass 3: the running 64.64 sum at every segment -> n_i = round(A_i) - round(A_{i-1}), seg_start[i] = round(A_{i-1})
 __global__ __launch_bounds__(kScanThreads) void k_len_apply(const double* __restrict__ st, const double* __restrict__ sp,
                                                              int64_t nseg, const U128* __restrict__ bsum,
                                                              int64_t* __restrict__ seg_start, PlanHeader* __restrict__ h) {
@@ -1723,6 +1635,8 @@ __global__ __launch_bounds__(kScanThreads) void k_len_apply(const double* __rest
       h->total_written = (int64_t)Ni;
     }
     if (amb) f |= kFlagAmbiguous;
+    // n_i < 2: the reference divides by zero / indexes an empty array -- if it ever gets there.  Downstream the segment
+    // counts as empty (S_i = 0, cannot straddle n_in); trim_body raises the flag unless the trim fires in front of it.
     if (Ni < Np + 2ull) atomicMin(&h->first_bad, (unsigned long long)i);
   }
   if (f) atomicOr(&h->flags, f);
@@ -1741,7 +1655,8 @@ __global__ __launch_bounds__(kScanThreads) void k_offs_reduce(const double* __re
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
-// the parity-translation element of step i from the approximate offsets around it (k_off_prepare's body)
+// the parity-translation element of step i (x_i -> x_{i+1}) from the approximate offsets xa, xb around it; a step that
+// is not provably inside one binade comes back !interior (the caller lists it `direct`)
 __device__ __forceinline__ PElem off_element(double xa, double xb, double Si, bool* interior_out) {
   const double lo = 1.0 - 0x1p-30, hi = 1.0 + 0x1p-30;
   const int e = f64_exponent(xa);
@@ -1749,6 +1664,7 @@ __device__ __forceinline__ PElem off_element(double xa, double xb, double Si, bo
                   f64_exponent(xa * hi) == e && f64_exponent(xb * lo) == e && f64_exponent(xb * hi) == e;
   PElem p{0, 0, 0, 0};
   if (interior) {
+    // u = ulp in binade e = 2^(e-1075); S/u is an exact power-of-two scaling
     const double t = ldexp(Si, 1075 - e);
     if (t < 0x1p62) {
       const double fl = floor(t);
@@ -1768,9 +1684,9 @@ __device__ __forceinline__ PElem off_element(double xa, double xb, double Si, bo
   return p;
 }
 
-// offsets, pass 3 of the float64 scan fused with k_off_prepare: the running sum in front of and behind every step is the
-// approximate offset there (a PREDICTION of its binade, verified later by k_off_apply: any accurate association of the
-// sum serves), from which the step's parity-translation element follows -- or the step is listed `direct`.
+// offsets, pass 3 of the float64 scan with off_element inside: the running sum in front of and behind every step is the
+// approximate offset there (a PREDICTION of its binade, verified later by off_apply_segment: any accurate association of
+// the sum serves), from which the step's parity-translation element follows -- or the step is listed `direct`.
 // Lazy plans (cand != nullptr): S holds closed-form sums good to lazy_bound(); a step whose element that uncertainty could
 // change -- S/ulp within the bound of a rounding boundary -- or that is not an interior step is listed for the exact sum.
 __global__ __launch_bounds__(kScanThreads) void k_offs_elements(const double* __restrict__ S, const double* __restrict__ st,
@@ -1880,11 +1796,11 @@ __global__ __launch_bounds__(64) void k_seg_exact_list(const double* __restrict_
   el[i] = p;
 }
 
-// offsets for every segment, verification of the binade prediction, end-trim detection (:129)
-__global__ void k_off_apply(const double* __restrict__ sp, const PElem* __restrict__ E, const RunEntry* __restrict__ runs,
-                            int64_t nseg, double n_in, double* __restrict__ seg_off, PlanHeader* __restrict__ h) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nseg || h->lazy_fail) return;
+// segment i: its offset (and the final one behind the last segment), verification of the binade prediction, end-trim
+// detection (:129)
+__device__ __forceinline__ void off_apply_segment(const double* __restrict__ sp, const PElem* __restrict__ E,
+                                                  const RunEntry* __restrict__ runs, int64_t i, int64_t nseg, double n_in,
+                                                  double* __restrict__ seg_off, PlanHeader* __restrict__ h) {
   const int nr = h->n_runs;
   int lo = 0, hi = nr - 1;                     // last run with start <= i
   while (lo < hi) {
@@ -1905,6 +1821,14 @@ __global__ void k_off_apply(const double* __restrict__ sp, const PElem* __restri
   }
   const double first = 1.0 / sp[i] + xi;       // k = 0: bs = 0/(n-1)*ds + s0 = s0
   if (first <= n_in && n_in <= xn) atomicMin(&h->trim_seg, (unsigned long long)i);
+}
+
+// offsets of a lazy plan: a thread per segment, the trim behind it in k_trim_lazy
+__global__ void k_off_apply(const double* __restrict__ sp, const PElem* __restrict__ E, const RunEntry* __restrict__ runs,
+                            int64_t nseg, double n_in, double* __restrict__ seg_off, PlanHeader* __restrict__ h) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nseg || h->lazy_fail) return;
+  off_apply_segment(sp, E, runs, i, nseg, n_in, seg_off, h);
 }
 
 // np.argmin |pos - n_in| inside the trim segment (first occurrence), header finalisation (one thread)
@@ -1975,13 +1899,6 @@ __device__ __forceinline__ void trim_body(const double* __restrict__ st, const d
   h->len_out = len;
 }
 
-__global__ void k_trim(const double* __restrict__ st, const double* __restrict__ sp, const int64_t* __restrict__ seg_start,
-                       const double* __restrict__ seg_off, int64_t m, double n_in, const double* __restrict__ ck,
-                       int64_t ck_len, PlanHeader* __restrict__ h) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  trim_body(st, sp, seg_start, seg_off, m, n_in, ck, ck_len, h);
-}
-
 // Lazy plans: the trim (it walks the trim segment from its first step: <= kLazyMaxN steps) and, since nothing behind it can
 // raise a flag any more, the verdict the record kernels and the host read: ck_valid = 2 (K_sinc may run; no checkpoints).
 __global__ void k_trim_lazy(const double* __restrict__ st, const double* __restrict__ sp, const int64_t* __restrict__ seg_start,
@@ -1996,7 +1913,7 @@ __global__ void k_trim_lazy(const double* __restrict__ st, const double* __restr
   h->ck_valid = ((fl & ~kFlagCapAmbiguous) || n_tiles + 1 > max_tiles) ? 0 : 2;
 }
 
-// k_off_apply with k_trim as the epilogue of the last block to finish (r04).  Grid-stride over the segments with at most 512
+// The eager plan's offsets, with the trim (trim_body) as the epilogue of the last block to finish.  Grid-stride over the segments with at most 512
 // blocks: every block ends with ONE atomic on the header's counter, and thousands of them serialise on that word (measured:
 // 0.4 ms for the 10 548 blocks of a 2.7 M-segment curve).
 __global__ __launch_bounds__(256) void k_off_apply_trim(const double* __restrict__ st, const double* __restrict__ sp,
@@ -2007,34 +1924,15 @@ __global__ __launch_bounds__(256) void k_off_apply_trim(const double* __restrict
   __shared__ int is_last;
   if (h->lazy_fail) return;           // not a curve for a lazy plan: it is being made again the eager way (and the
                                                  // trim's walk over a segment without checkpoints could take seconds)
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nseg; i += (int64_t)gridDim.x * blockDim.x) {
-    const int nr = h->n_runs;
-    int lo = 0, hi = nr - 1;                     // last run with start <= i
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (runs[mid].start <= i) lo = mid; else hi = mid - 1;
-    }
-    const long long a = runs[lo].start;
-    const double xa = runs[lo].x;
-    const double xi = (i == a) ? xa : apply_elem(E[i - 1], xa);
-    const bool is_direct = runs[lo + 1].start == i + 1;      // step i ends its run
-    const double xn = is_direct ? runs[lo + 1].x : apply_elem(E[i], xa);
-    seg_off[i] = xi;
-    if (i == nseg - 1) seg_off[nseg] = xn;
-    if (!is_direct) {
-      const int e = f64_exponent(xa);
-      if (f64_exponent(xi) != e || f64_exponent(xn) != e) atomicOr(&h->flags, kFlagVerify);
-    }
-    const double first = 1.0 / sp[i] + xi;       // k = 0: bs = 0/(n-1)*ds + s0 = s0
-    if (first <= n_in && n_in <= xn) atomicMin(&h->trim_seg, (unsigned long long)i);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nseg; i += (int64_t)gridDim.x * blockDim.x)
+    off_apply_segment(sp, E, runs, i, nseg, n_in, seg_off, h);
   __threadfence();
   __syncthreads();
-  if (threadIdx.x == 0) is_last = atomicAdd(&h->pad2, 1) == (int)gridDim.x - 1;
+  if (threadIdx.x == 0) is_last = atomicAdd(&h->done_off_apply_trim, 1) == (int)gridDim.x - 1;
   __syncthreads();
   if (!is_last || threadIdx.x != 0) return;
   __threadfence();                               // acquire: the other blocks' seg_off and header atomics
-  h->pad2 = 0;
+  h->done_off_apply_trim = 0;
   trim_body(st, sp, seg_start, seg_off, nseg + 1, n_in, ck, ck_len, h);
 }
 
@@ -2152,7 +2050,7 @@ static int host_lengths(const PlanView& pv, const double* d_st, const double* d_
       *ok = false;
       return PAR_OK;
     }
-    if (rn < 2.0 && first_bad == kNoTrim) first_bad = (unsigned long long)i;   // harmless behind the trim: k_trim decides
+    if (rn < 2.0 && first_bad == kNoTrim) first_bad = (unsigned long long)i;   // harmless behind the trim: trim_body decides
     err = inerr - rn;
     start[i] = acc;
     acc += (int64_t)rn;
@@ -2240,9 +2138,9 @@ static int host_plan(const PlanView& pv, const double* d_st, const double* d_sp,
   out->speed_sum = sum;
   out->ck_len = 0;
   out->ck_valid = 0;
-  out->pad2 = 0;
+  out->done_off_apply_trim = 0;
   out->n_long = 0;          // counted afresh by k_count_long when the checkpoints are redone for this segmentation
-  out->pad3 = 0;
+  out->done_tile_seg_publish = 0;
   out->written = acc;
   out->first_bad = kNoTrim;
   PAR_HIP_CHECK(hipMemcpyAsync(pv.seg_start, start.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -2307,32 +2205,20 @@ extern "C" {
 
 size_t par_speed_plan_bytes(int64_t m) { return par::plan_bytes(m < 2 ? 2 : m); }
 
-// Per-segment reciprocal sums (+ checkpoints): one lane per ordinary segment, the chunked exact path for long ones.
-// mode 0: count the long segments, read the count back and run the chunked-cumsum kernels if there are any (the serial-path
-//         plans: a stream synchronisation in the middle);
-// mode 1: k_seg_sum counts its long segments itself and nothing else happens here -- the caller finds the count in the
-//         header it reads at the end of the plan and, if it is not zero, makes the plan again in mode 2;
-// mode 2: the chunked-cumsum kernels unconditionally.
-static int launch_seg_sums(const double* speeds, const par::PlanView& pv, int64_t nseg, double* ck, int64_t ck_len,
-                            int64_t max_out, int64_t m, hipStream_t s, int mode = 0) {
+// Per-segment reciprocal sums (+ checkpoints), one lane per ordinary segment.  Long segments are left to the chunked-cumsum
+// kernels; count_long says what k_seg_sum does about the ones it meets: 0 nothing (the serial path has counted them with
+// k_count_long); 1 counts them in the header and voids the rest of the pass (the caller finds the count in the header it reads
+// at the end of the go and makes the plan again with the chunked-cumsum kernels in); 2 counts them (that second go).
+static void enqueue_seg_sum(const double* speeds, const par::PlanView& pv, int64_t nseg, double* ck, int64_t ck_len,
+                            int count_long, hipStream_t s) {
+  hipLaunchKernelGGL(par::k_seg_sum, dim3((unsigned)par::ceil_div(nseg, 64)), dim3(64), 0, s, speeds, pv.seg_start, nseg, pv.S,
+                     ck, ck_len, pv.hdr, count_long);
+}
+
+// The chunked exact cumsum of the long segments, behind k_seg_sum (needs the checkpoint buffer)
+static void enqueue_long_segments(const double* speeds, const par::PlanView& pv, int64_t nseg, double* ck, int64_t ck_len,
+                                  int64_t max_out, int64_t m, hipStream_t s) {
   using namespace par;
-  const unsigned g256 = (unsigned)ceil_div(nseg, 256);
-  if (ck && mode == 0) hipLaunchKernelGGL(k_count_long, dim3(g256), dim3(256), 0, s, pv.seg_start, nseg, (const double*)ck, ck_len, pv.hdr);
-  hipLaunchKernelGGL(k_seg_sum, dim3((unsigned)ceil_div(nseg, 64)), dim3(64), 0, s, speeds, pv.seg_start, nseg, pv.S, ck,
-                     ck_len, pv.hdr, mode);
-  if (!ck || mode == 1) return PAR_OK;
-  if (mode == 2) goto long_kernels;
-  // Curves without a long segment (every dense curve) skip the nine chunked-cumsum launches: one 4-byte read-back,
-  // issued behind k_seg_sum so the GPU stays busy while the host waits.  (It is not only the launches: under a
-  // concurrent K_sinc the side stream is served well for about a millisecond and then starves until K_sinc
-  // drains -- measured --, so a plan that is to hide under the previous file's K_sinc has to be short.)
-  {
-    int n_long = 0;
-    PAR_HIP_CHECK(hipMemcpyAsync(&n_long, &pv.hdr->n_long, sizeof(int), hipMemcpyDeviceToHost, s));
-    PAR_HIP_CHECK(hipStreamSynchronize(s));
-    if (n_long == 0) return PAR_OK;
-  }
-long_kernels:
   const long long G = max_out / kLongChunk + m + 8;                 // bound on the global chunk slots
   const long long GW = G / kWinSlotDiv + 8;                         // ... and on the global window slots
   const unsigned gc = (unsigned)ceil_div(G, 256), gs = (unsigned)(nseg < 2048 ? nseg : 2048),
@@ -2346,7 +2232,6 @@ long_kernels:
   hipLaunchKernelGGL(k_long_stitch, dim3(gs), dim3(256), 0, s, speeds, pv.seg_start, nseg, ck, ck_len, pv.hdr);
   hipLaunchKernelGGL(k_long_wapply, dim3(gw), dim3(256), 0, s, pv.seg_start, nseg, ck, ck_len, GW, pv.hdr);
   hipLaunchKernelGGL(k_long_final, dim3(gc), dim3(256), 0, s, speeds, pv.seg_start, nseg, pv.S, ck, ck_len, G, pv.hdr);
-  return PAR_OK;
 }
 
 // block records + tile headers for every block that may hold outputs (the kernel reads len_out on the device)
@@ -2362,7 +2247,98 @@ static void launch_block_rec(const double* speeds, const par::PlanView& pv, int6
                      (const SegFast*)a.seg_fast, (const TileHdr*)a.hdr, a.rec, a.rec2, (const PlanHeader*)pv.hdr);
 }
 
-// Shared implementation.  aux (optional, device): cumsum checkpoints for the fused resampler.
+// What one go at the device plan is made with.  plan_impl starts with the last two false and, when the header of a finished
+// go asks for it, changes one member and goes again.
+struct PlanGo {
+  bool lazy;           // closed-form segment sums, exact ones only where a rounding decides (pos_plan.h, "lazy plans")
+  bool with_long;      // the chunked-cumsum kernels are in: the go before found long segments
+  bool host_lengths;   // the O(m) length recurrence is redone serially on the host in the reference's own float64 order (the go
+                       // before met a near-tie); the O(len_out) reciprocal sums, offsets, trim, checkpoints stay on the device
+};
+
+// One go, enqueued on s.  *lengths_ok = false, and nothing behind the lengths enqueued: the host recurrence met a negative or
+// absurd length.  aux (optional, device): checkpoints, tile tables and block records for the fused resampler.
+static int enqueue_device_pass(const PlanGo& go, const double* sampletimes, const double* speeds, int64_t m, int64_t n_in,
+                               const par::PlanView& pv, void* aux, int64_t max_out, hipStream_t s, bool* lengths_ok) {
+  using namespace par;
+  const int64_t nseg = m - 1;
+  const FusedAux av = aux ? fused_aux_view(aux, max_out, m) : FusedAux{};
+  const int64_t ck_len = aux ? (int64_t)fused_ck_len(max_out, m) : 0;
+  const int64_t max_tiles = aux ? (int64_t)fused_tiles(max_out) : 0;
+  const unsigned g256 = (unsigned)ceil_div(nseg, 256);
+  const unsigned nbs = (unsigned)ceil_div(nseg, kScanTile), nbm = (unsigned)ceil_div(m, kScanTile);
+  double* scratch_f = pv.scratch_f;             // per-wave speed partials, later the float64 scan's block sums
+  *lengths_ok = true;
+  hipLaunchKernelGGL(k_init_header, dim3(1), dim3(1), 0, s, pv.hdr, m, go.lazy ? 1 : 0);
+  if (aux) PAR_HIP_CHECK(hipMemsetAsync(av.redo_count, 0, 64, s));   // K_sinc's tile list: empty until a launch fills it
+  if (!go.host_lengths) {
+    // lengths: the 64.64 fixed-point scan with want_fixed, the rounding and the speed sum inside its passes (3 launches)
+    U128* bsum = reinterpret_cast<U128*>(pv.bsum);
+    hipLaunchKernelGGL(k_len_reduce, dim3(nbm), dim3(kScanThreads), 0, s, sampletimes, speeds, nseg, bsum, scratch_f, pv.hdr);
+    hipLaunchKernelGGL(k_len_top, dim3(1), dim3(kScanThreads), 0, s, bsum, (int64_t)nbs, (const double*)scratch_f,
+                       (int64_t)nbm * (kScanThreads / kWave), pv.hdr);
+    hipLaunchKernelGGL(k_len_apply, dim3(nbs), dim3(kScanThreads), 0, s, sampletimes, speeds, nseg, (const U128*)bsum,
+                       pv.seg_start, pv.hdr);
+  } else {
+    const int rc = host_lengths(pv, sampletimes, speeds, m, s, lengths_ok);
+    if (rc != PAR_OK || !*lengths_ok) return rc;
+    hipLaunchKernelGGL(k_speed_sum, dim3((unsigned)(m / 4096 + 1)), dim3(256), 0, s, speeds, m,
+                       reinterpret_cast<double*>(pv.bsum), pv.hdr);
+  }
+  if (go.lazy) {
+    hipLaunchKernelGGL(k_seg_sum_lazy, dim3(g256), dim3(256), 0, s, speeds, (const int64_t*)pv.seg_start, nseg, pv.S, pv.hdr);
+  } else {
+    enqueue_seg_sum(speeds, pv, nseg, av.ck, ck_len, go.with_long ? 2 : 1, s);
+    if (go.with_long) enqueue_long_segments(speeds, pv, nseg, av.ck, ck_len, max_out, m, s);   // (only a plan with an aux buffer finds any)
+  }
+  // offsets: float64 scan of S (its apply pass makes the parity-translation elements), heads, ComposeP scan, the stitch,
+  // then the offsets themselves and the trim
+  PElem* el = reinterpret_cast<PElem*>(pv.scan);
+  hipLaunchKernelGGL(k_offs_reduce, dim3(nbs), dim3(kScanThreads), 0, s, (const double*)pv.S, nseg, scratch_f);
+  hipLaunchKernelGGL(k_scan_top<AddF64>, dim3(1), dim3(kScanThreads), 0, s, scratch_f, (int64_t)nbs);
+  hipLaunchKernelGGL(k_offs_elements, dim3(nbs), dim3(kScanThreads), 0, s, (const double*)pv.S, sampletimes, nseg,
+                     (const double*)scratch_f, el, pv.direct, pv.hdr, go.lazy ? pv.cand : (Cand*)nullptr, speeds,
+                     (const int64_t*)pv.seg_start);
+  if (go.lazy)
+    hipLaunchKernelGGL(k_seg_exact_list, dim3(kMaxCand / 64), dim3(64), 0, s, speeds, (const int64_t*)pv.seg_start, nseg, pv.S,
+                       el, (const Cand*)pv.cand, pv.direct, pv.hdr);
+  hipLaunchKernelGGL(k_off_heads, dim3((kMaxDirect + 255) / 256), dim3(256), 0, s, el, nseg, pv.direct, pv.hdr);
+  hipLaunchKernelGGL(k_scan_reduce<ComposeP>, dim3(nbs), dim3(kScanThreads), 0, s, (const PElem*)el, nseg,
+                     reinterpret_cast<PElem*>(pv.bsum));
+  hipLaunchKernelGGL(k_scan_top<ComposeP>, dim3(1), dim3(kScanThreads), 0, s, reinterpret_cast<PElem*>(pv.bsum), (int64_t)nbs);
+  hipLaunchKernelGGL(k_scan_apply<ComposeP>, dim3(nbs), dim3(kScanThreads), 0, s, el, nseg, (const PElem*)pv.bsum);
+  hipLaunchKernelGGL(k_off_stitch, dim3(1), dim3(1), 0, s, pv.S, el, sampletimes, nseg, pv.direct, pv.runs, pv.hdr);
+  if (go.lazy) {
+    // full grids without the last-block epilogues (their one atomic per block on a header word is what capped those grids)
+    hipLaunchKernelGGL(k_off_apply, dim3(g256), dim3(256), 0, s, speeds, (const PElem*)el, (const RunEntry*)pv.runs, nseg,
+                       (double)n_in, pv.seg_off, pv.hdr);
+    hipLaunchKernelGGL(k_trim_lazy, dim3(1), dim3(1), 0, s, sampletimes, speeds, (const int64_t*)pv.seg_start,
+                       (const double*)pv.seg_off, m, (double)n_in, ck_len, max_tiles, pv.hdr);
+    hipLaunchKernelGGL(k_tile_seg_lazy, dim3(g256), dim3(256), 0, s, speeds, (const int64_t*)pv.seg_start,
+                       (const double*)pv.seg_off, nseg, av.tile_seg, av.seg_fast, av.tile_st, av.hdr, (const PlanHeader*)pv.hdr);
+    hipLaunchKernelGGL(k_block_rec_lazy, dim3((unsigned)ceil_div(nseg, 4 * kRecLazySegs)), dim3(256), 0, s, speeds, (const int64_t*)pv.seg_start, nseg,
+                       (const SegFast*)av.seg_fast, (const TileHdr*)av.hdr, av.rec, av.rec2, (const PlanHeader*)pv.hdr);
+  } else {
+    hipLaunchKernelGGL(k_off_apply_trim, dim3(g256 < 512u ? g256 : 512u), dim3(256), 0, s, sampletimes, speeds, (const PElem*)el,
+                       (const RunEntry*)pv.runs, (const int64_t*)pv.seg_start, nseg, (double)n_in, pv.seg_off,
+                       (const double*)av.ck, ck_len, pv.hdr);
+    if (aux) {
+      const int64_t n_items = std::max<int64_t>(nseg, max_tiles);
+      hipLaunchKernelGGL(k_tile_seg_publish, dim3((unsigned)std::min<int64_t>(ceil_div(n_items, 256), 512)), dim3(256), 0, s,
+                         speeds, pv.seg_start, pv.seg_off, nseg, (const double*)av.ck, ck_len, max_tiles, av.tile_seg,
+                         av.seg_fast, av.tile_st, av.hdr, pv.hdr, n_items);
+      launch_block_rec(speeds, pv, nseg, aux, max_out, m, s);
+    }
+  }
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+// force_host (include/par_hip.h): the low two bits ask for the serial chain, 2 of them with the injected verify fault (fused
+// form, tests only); 8 asks for the eager plan
+constexpr int kForceSerialChain = 3, kForceVerifyFault = 2, kForceEager = 8;
+
+// Shared implementation: validate, go at the device plan until its header settles, else the serial path; results.
 static thread_local int g_last_plan_flags = 0;
 
 static int plan_impl(int device, const double* sampletimes, const double* speeds, int64_t m, int64_t n_in, void* work,
@@ -2379,142 +2355,71 @@ static int plan_impl(int device, const double* sampletimes, const double* speeds
   hipStream_t s = as_stream(stream);
   const int64_t nseg = m - 1;
   PlanView pv = plan_view(work, m);
-  double* ck = static_cast<double*>(aux);
-  const int64_t ck_len = aux ? (int64_t)fused_ck_len(max_out, m) : 0;
-  const int64_t max_tiles = aux ? (int64_t)fused_tiles(max_out) : 0;
   PlanHeader h;
   memset(&h, 0, sizeof(h));
-  bool need_host = (force_host & 3) != 0;
-  // lazy plan (pos_plan.h): closed-form segment sums, exact ones only where a rounding decides -- for the fused resampler on
-  // dense, gentle curves (every segment checked on the device; a curve that is not one is planned again the eager way).
-  // force_host & 8 asks for the eager plan outright (callers that fill positions from the checkpoints).
-  bool lazy = aux != nullptr && !need_host && !(force_host & 8) && n_in / (m - 1) <= kLazyMaxN;
+  bool serial = (force_host & kForceSerialChain) != 0;
+  // lazy plan (pos_plan.h): for the fused resampler on dense, gentle curves (every segment checked on the device; a curve that
+  // is not one is planned again the eager way).  kForceEager asks for the eager plan outright (callers that fill positions
+  // from the checkpoints).
+  PlanGo go{aux != nullptr && !serial && !(force_host & kForceEager) && n_in / (m - 1) <= kLazyMaxN, false, false};
   g_last_plan_flags = 0;
-  // attempt 0: everything on the device.  attempt 1 (only after a near-tie in the segment lengths): the O(m) length
-  // recurrence is redone serially on the host in the reference's own float64 order, everything else -- the O(len_out)
-  // reciprocal sums, offsets, trim, checkpoints -- stays on the device.
-  bool host_made_lengths = false;
-  bool with_long = false;                       // the plan holds long segments: found out from the header of the first go
-  for (int attempt = 0; attempt < 2 && !need_host; ++attempt) {
-    const unsigned g256 = (unsigned)ceil_div(nseg, 256);
-    const unsigned nbs = (unsigned)ceil_div(nseg, kScanTile), nbm = (unsigned)ceil_div(m, kScanTile);
-    double* scratch_f = pv.xs;                  // per-wave speed partials, later the float64 scan's block sums (xs itself is gone)
-    hipLaunchKernelGGL(k_init_header, dim3(1), dim3(1), 0, s, pv.hdr, m, lazy ? 1 : 0);
-    if (aux) PAR_HIP_CHECK(hipMemsetAsync(fused_aux_view(aux, max_out, m).redo_count, 0, 64, s));   // K_sinc's tile list: empty until a launch fills it
-    int rc;
-    if (attempt == 0) {
-      // lengths: the 64.64 fixed-point scan with k_seg_want / k_seg_lengths / k_speed_sum inside its passes (3 launches)
-      U128* bsum = reinterpret_cast<U128*>(pv.bsum);
-      hipLaunchKernelGGL(k_len_reduce, dim3(nbm), dim3(kScanThreads), 0, s, sampletimes, speeds, nseg, bsum, scratch_f, pv.hdr);
-      hipLaunchKernelGGL(k_len_top, dim3(1), dim3(kScanThreads), 0, s, bsum, (int64_t)nbs, (const double*)scratch_f,
-                         (int64_t)nbm * (kScanThreads / kWave), pv.hdr);
-      hipLaunchKernelGGL(k_len_apply, dim3(nbs), dim3(kScanThreads), 0, s, sampletimes, speeds, nseg, (const U128*)bsum,
-                         pv.seg_start, pv.hdr);
-    } else {
-      bool lengths_ok = false;
-      rc = host_lengths(pv, sampletimes, speeds, m, s, &lengths_ok);
-      if (rc != PAR_OK) return rc;
-      if (!lengths_ok) {                 // a negative or absurd length: the serial path words the diagnosis
-        need_host = true;
-        break;
-      }
-      host_made_lengths = true;
-      hipLaunchKernelGGL(k_speed_sum, dim3((unsigned)(m / 4096 + 1)), dim3(256), 0, s, speeds, m,
-                         reinterpret_cast<double*>(pv.bsum), pv.hdr);
+  while (!serial) {
+    bool lengths_ok;
+    const int rc = enqueue_device_pass(go, sampletimes, speeds, m, n_in, pv, aux, max_out, s, &lengths_ok);
+    if (rc != PAR_OK) return rc;
+    if (!lengths_ok) {                          // the serial path words the diagnosis
+      serial = true;
+      break;
     }
-    if (lazy) {
-      hipLaunchKernelGGL(k_seg_sum_lazy, dim3(g256), dim3(256), 0, s, speeds, (const int64_t*)pv.seg_start, nseg, pv.S, pv.hdr);
-    } else {
-      rc = launch_seg_sums(speeds, pv, nseg, ck, ck_len, max_out, m, s, with_long ? 2 : 1);
-      if (rc != PAR_OK) return rc;
-    }
-    // offsets: float64 scan of S (its apply pass makes the parity-translation elements), heads, ComposeP scan (its apply
-    // pass ends with the stitch), then the offsets themselves with the trim as epilogue: 8 launches
-    PElem* el = reinterpret_cast<PElem*>(pv.scan);
-    hipLaunchKernelGGL(k_offs_reduce, dim3(nbs), dim3(kScanThreads), 0, s, (const double*)pv.S, nseg, scratch_f);
-    hipLaunchKernelGGL(k_scan_top<AddF64>, dim3(1), dim3(kScanThreads), 0, s, scratch_f, (int64_t)nbs);
-    hipLaunchKernelGGL(k_offs_elements, dim3(nbs), dim3(kScanThreads), 0, s, (const double*)pv.S, sampletimes, nseg,
-                       (const double*)scratch_f, el, pv.direct, pv.hdr, lazy ? pv.cand : (Cand*)nullptr, speeds,
-                       (const int64_t*)pv.seg_start);
-    if (lazy)
-      hipLaunchKernelGGL(k_seg_exact_list, dim3(kMaxCand / 64), dim3(64), 0, s, speeds, (const int64_t*)pv.seg_start, nseg, pv.S,
-                         el, (const Cand*)pv.cand, pv.direct, pv.hdr);
-    hipLaunchKernelGGL(k_off_heads, dim3((kMaxDirect + 255) / 256), dim3(256), 0, s, el, nseg, pv.direct, pv.hdr);
-    hipLaunchKernelGGL(k_scan_reduce<ComposeP>, dim3(nbs), dim3(kScanThreads), 0, s, (const PElem*)el, nseg,
-                       reinterpret_cast<PElem*>(pv.bsum));
-    hipLaunchKernelGGL(k_scan_top<ComposeP>, dim3(1), dim3(kScanThreads), 0, s, reinterpret_cast<PElem*>(pv.bsum), (int64_t)nbs);
-    hipLaunchKernelGGL(k_scan_apply<ComposeP>, dim3(nbs), dim3(kScanThreads), 0, s, el, nseg, (const PElem*)pv.bsum);
-    hipLaunchKernelGGL(k_off_stitch, dim3(1), dim3(1), 0, s, pv.S, el, sampletimes, nseg, pv.direct, pv.runs, pv.hdr);
-    if (lazy) {
-      // full grids without the last-block epilogues (their one atomic per block on a header word is what capped those grids)
-      hipLaunchKernelGGL(k_off_apply, dim3(g256), dim3(256), 0, s, speeds, (const PElem*)el, (const RunEntry*)pv.runs, nseg,
-                         (double)n_in, pv.seg_off, pv.hdr);
-      hipLaunchKernelGGL(k_trim_lazy, dim3(1), dim3(1), 0, s, sampletimes, speeds, (const int64_t*)pv.seg_start,
-                         (const double*)pv.seg_off, m, (double)n_in, ck_len, max_tiles, pv.hdr);
-      const FusedAux av = fused_aux_view(aux, max_out, m);
-      hipLaunchKernelGGL(k_tile_seg_lazy, dim3(g256), dim3(256), 0, s, speeds, (const int64_t*)pv.seg_start,
-                         (const double*)pv.seg_off, nseg, av.tile_seg, av.seg_fast, av.tile_st, av.hdr, (const PlanHeader*)pv.hdr);
-      hipLaunchKernelGGL(k_block_rec_lazy, dim3((unsigned)ceil_div(nseg, 4 * kRecLazySegs)), dim3(256), 0, s, speeds, (const int64_t*)pv.seg_start, nseg,
-                         (const SegFast*)av.seg_fast, (const TileHdr*)av.hdr, av.rec, av.rec2, (const PlanHeader*)pv.hdr);
-    } else {
-    hipLaunchKernelGGL(k_off_apply_trim, dim3(g256 < 512u ? g256 : 512u), dim3(256), 0, s, sampletimes, speeds, (const PElem*)el,
-                       (const RunEntry*)pv.runs, (const int64_t*)pv.seg_start, nseg, (double)n_in, pv.seg_off,
-                       (const double*)ck, ck_len, pv.hdr);
-    }
-    if (aux && !lazy) {
-      const int64_t n_items = std::max<int64_t>(nseg, max_tiles);
-      hipLaunchKernelGGL(k_tile_seg_publish, dim3((unsigned)std::min<int64_t>(ceil_div(n_items, 256), 512)), dim3(256), 0, s,
-                         speeds, pv.seg_start, pv.seg_off, nseg, (const double*)ck, ck_len, max_tiles,
-                         reinterpret_cast<int64_t*>(ck + ck_len), reinterpret_cast<SegFast*>(ck + ck_len + max_tiles),
-                         fused_aux_view(aux, max_out, m).tile_st, fused_aux_view(aux, max_out, m).hdr, pv.hdr, n_items,
-                         lazy ? 1 : 0);
-      launch_block_rec(speeds, pv, nseg, aux, max_out, m, s);
-    }
-    PAR_HIP_CHECK(hipGetLastError());
     PAR_HIP_CHECK(hipMemcpyAsync(&h, pv.hdr, sizeof(h), hipMemcpyDeviceToHost, s));
     PAR_HIP_CHECK(hipStreamSynchronize(s));
-    if (lazy && h.lazy_fail) {                  // not a curve for a lazy plan: once more, with the per-sample cumsum
-      lazy = false;
-      --attempt;
-      continue;
+    if (go.lazy && h.lazy_fail) {
+      go.lazy = false;                          // not a curve for a lazy plan: once more, with the per-sample cumsum
+    } else if (h.n_long > 0 && !go.with_long) {
+      go.with_long = true;                      // sparse curve: once more, with the chunked exact cumsum of its long segments
+    } else {
+      if (h.flags & kFlagCapAmbiguous) {
+        // Only the buffer bound is in doubt: settle int(mean * span * 1.01) with numpy's own pairwise order on the host
+        // (one D2H of the speed samples); everything else the device computed stands.
+        std::vector<double> sp_h(m);
+        double ends[2];
+        PAR_HIP_CHECK(hipMemcpyAsync(sp_h.data(), speeds, m * sizeof(double), hipMemcpyDeviceToHost, s));
+        PAR_HIP_CHECK(hipMemcpyAsync(&ends[0], sampletimes, sizeof(double), hipMemcpyDeviceToHost, s));
+        PAR_HIP_CHECK(hipMemcpyAsync(&ends[1], sampletimes + (m - 1), sizeof(double), hipMemcpyDeviceToHost, s));
+        PAR_HIP_CHECK(hipStreamSynchronize(s));
+        h.cap = (int64_t)((np_pairwise_sum(sp_h.data(), m) / (double)m) * (ends[1] - ends[0]) * 1.01);
+        h.flags &= ~kFlagCapAmbiguous;
+        PAR_HIP_CHECK(hipMemcpyAsync(pv.hdr, &h, sizeof(h), hipMemcpyHostToDevice, s));
+        PAR_HIP_CHECK(hipStreamSynchronize(s));
+      }
+      g_last_plan_flags |= h.flags;
+      if (h.flags == 0) break;                  // done
+      // a near-tie in the lengths alone: once more, with host-made lengths; anything else (n_i < 2, range, verification,
+      // too many crossings, or a second failure): the serial path decides -- it also produces the reference's own
+      // diagnosis for genuinely bad curves.
+      if (h.flags == kFlagAmbiguous && !go.host_lengths) go.host_lengths = true;
+      else serial = true;
     }
-    if (h.n_long > 0 && !with_long) {           // sparse curve: once more, with the chunked exact cumsum of its long segments
-      with_long = true;
-      --attempt;
-      continue;
-    }
-    if (h.flags & kFlagCapAmbiguous) {
-      // Only the buffer bound is in doubt: settle int(mean * span * 1.01) with numpy's own pairwise order on the host
-      // (one D2H of the speed samples); everything else the device computed stands.
-      std::vector<double> sp_h(m);
-      double ends[2];
-      PAR_HIP_CHECK(hipMemcpyAsync(sp_h.data(), speeds, m * sizeof(double), hipMemcpyDeviceToHost, s));
-      PAR_HIP_CHECK(hipMemcpyAsync(&ends[0], sampletimes, sizeof(double), hipMemcpyDeviceToHost, s));
-      PAR_HIP_CHECK(hipMemcpyAsync(&ends[1], sampletimes + (m - 1), sizeof(double), hipMemcpyDeviceToHost, s));
-      PAR_HIP_CHECK(hipStreamSynchronize(s));
-      h.cap = (int64_t)((np_pairwise_sum(sp_h.data(), m) / (double)m) * (ends[1] - ends[0]) * 1.01);
-      h.flags &= ~kFlagCapAmbiguous;
-      PAR_HIP_CHECK(hipMemcpyAsync(pv.hdr, &h, sizeof(h), hipMemcpyHostToDevice, s));
-      PAR_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    if (h.flags == 0) break;
-    g_last_plan_flags |= h.flags;
-    // a near-tie in the lengths alone: one more round with host-made lengths; anything else (n_i < 2, range,
-    // verification, too many crossings, or a second failure): the serial path decides -- it also produces the
-    // reference's own diagnosis for genuinely bad curves.
-    if (!(attempt == 0 && h.flags == kFlagAmbiguous)) need_host = true;
   }
-  if (need_host) {
+  if (serial) {
     int rc = host_plan(pv, sampletimes, speeds, m, n_in, &h, s);
     if (rc != PAR_OK) return rc;
     if (aux) {     // checkpoints + tile map for the serial path's segmentation: same exact device arithmetic
-      rc = launch_seg_sums(speeds, pv, nseg, ck, ck_len, max_out, m, s);
-      if (rc != PAR_OK) return rc;
+      const FusedAux av = fused_aux_view(aux, max_out, m);
+      const int64_t ck_len = (int64_t)fused_ck_len(max_out, m), max_tiles = (int64_t)fused_tiles(max_out);
+      hipLaunchKernelGGL(k_count_long, dim3((unsigned)ceil_div(nseg, 256)), dim3(256), 0, s, pv.seg_start, nseg,
+                         (const double*)av.ck, ck_len, pv.hdr);
+      enqueue_seg_sum(speeds, pv, nseg, av.ck, ck_len, 0, s);
+      // Curves without a long segment (every dense curve) skip the nine chunked-cumsum launches: one 4-byte read-back,
+      // issued behind k_seg_sum so the GPU stays busy while the host waits.
+      int n_long = 0;
+      PAR_HIP_CHECK(hipMemcpyAsync(&n_long, &pv.hdr->n_long, sizeof(int), hipMemcpyDeviceToHost, s));
+      PAR_HIP_CHECK(hipStreamSynchronize(s));
+      if (n_long > 0) enqueue_long_segments(speeds, pv, nseg, av.ck, ck_len, max_out, m, s);
       hipLaunchKernelGGL(k_tile_seg, dim3((unsigned)ceil_div(std::max<int64_t>(nseg, max_tiles), 256)), dim3(256), 0, s,
-                         speeds, pv.seg_start, pv.seg_off, nseg, (const double*)ck, ck_len, max_tiles,
-                         reinterpret_cast<int64_t*>(ck + ck_len), reinterpret_cast<SegFast*>(ck + ck_len + max_tiles),
-                         fused_aux_view(aux, max_out, m).tile_st, fused_aux_view(aux, max_out, m).hdr, pv.hdr);
-      if ((force_host & 3) == 2) hipLaunchKernelGGL(k_inject_verify_fault, dim3(1), dim3(1), 0, s, pv.hdr);
+                         speeds, pv.seg_start, pv.seg_off, nseg, (const double*)av.ck, ck_len, max_tiles, av.tile_seg,
+                         av.seg_fast, av.tile_st, av.hdr, pv.hdr);
+      if ((force_host & kForceSerialChain) == kForceVerifyFault) hipLaunchKernelGGL(k_inject_verify_fault, dim3(1), dim3(1), 0, s, pv.hdr);
       hipLaunchKernelGGL(k_publish_ck, dim3(1), dim3(1), 0, s, pv.hdr, ck_len);
       launch_block_rec(speeds, pv, nseg, aux, max_out, m, s);
       PAR_HIP_CHECK(hipGetLastError());
@@ -2528,7 +2433,7 @@ static int plan_impl(int device, const double* sampletimes, const double* speeds
                 "par_speed_to_pos_plan: positions overflow the reference's end_guess buffer (%lld > %lld); it raises here",
                 (long long)h.written, (long long)h.cap);
   }
-  if (path_used) *path_used = need_host ? 1 : (host_made_lengths ? 2 : 0);
+  if (path_used) *path_used = serial ? 1 : (go.host_lengths ? 2 : 0);
   if (fused_ok) *fused_ok = aux ? h.ck_valid : 0;
   *len_out = h.len_out;
   *trimmed = h.trimmed;

@@ -18,12 +18,12 @@ struct PlanHeader {
   double speed_sum;
   int64_t ck_len;         // checkpoint slots available in the caller's aux buffer (0: none)
   int32_t ck_valid;       // 1: the aux buffer holds this plan's cumsum checkpoints (fused resampler may run)
-  int32_t pad2;
+  int32_t done_off_apply_trim;    // blocks of k_off_apply_trim (in front of it, of k_speed_sum) that have finished: the last one resets it
   int64_t written;        // outputs the reference has written into its buffer when it stops (end of the trim segment)
   int32_t n_long;         // segments handled by the chunked exact cumsum (sparse curves), see pos.hip
-  int32_t pad3;
+  int32_t done_tile_seg_publish;  // blocks of k_tile_seg_publish that have finished: the last one publishes ck_valid and resets it
   unsigned long long first_bad;  // first segment with n_i < 2 (~0: none).  Harmless when the trim fires before it: the
-                                 // reference stops there and never builds that segment (k_trim decides)
+                                 // reference stops there and never builds that segment (trim_body in pos.hip decides)
   int32_t lazy;           // 1: this plan was made WITHOUT the per-sample cumsum (closed-form segment sums, see "lazy plans")
   int32_t lazy_fail;      // != 0: this pass is void and the kernels behind the mark leave at once -- 1 / 2: some segment is outside
                           //       what the closed form vouches for / too many candidates (the caller makes the plan again the
@@ -68,7 +68,7 @@ struct PlanView {
   int64_t* seg_start;   // [m]   seg_start[i] = outputs before segment i; [m-1] = total
   double* seg_off;      // [m]   offset chain; seg_off[i] = position offset of segment i; [m-1] = final
   double* S;            // [m]   per-segment reciprocal sums
-  double* xs;           // [m]   approx offsets (plain f64 scan)
+  double* scratch_f;    // [m]   float64 scratch: per-wave partials of the speed sum, then the block sums of the plain f64 scan of S
   char* scan;           // [m * 32] scan elements (U128 then PElem)
   char* bsum;           // block sums for the scans
   long long* direct;    // [kMaxDirect] indices of direct (binade-crossing) steps
@@ -91,7 +91,7 @@ inline PlanView plan_view(void* work, int64_t m) {
   b += (size_t)m * 8;
   v.S = reinterpret_cast<double*>(b);
   b += (size_t)m * 8;
-  v.xs = reinterpret_cast<double*>(b);
+  v.scratch_f = reinterpret_cast<double*>(b);
   b += (size_t)m * 8;
   v.scan = b;
   b += (size_t)m * 32;

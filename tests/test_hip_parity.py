@@ -2713,6 +2713,10 @@ def test_lazy_plan_equals_eager_plan(par):
     cases.append(("no-trim", st, sp, int(st[-1] * 1.2), True))            # the trim never fires
     st5 = np.arange(40) * 5000.0                                           # segments of ~5000 outputs: too long for the closed form
     cases.append(("long-segs", st5, 1.0 + 0.002 * np.sin(np.arange(40) * 0.3), int(st5[-1] * 0.97), False))
+    # dense on average (850 inputs per segment: tried lazy) with ONE segment above the chunked cumsum's threshold: the plan is made
+    # three times -- lazy, eager, eager with the long-segment kernels
+    st6 = np.concatenate(([0.0], np.cumsum([256.0] * 31 + [40000.0] + [256.0] * 32)))
+    cases.append(("mixed-long", st6, 1.0 + 0.01 * np.sin(0.7 * np.arange(65)), int(st6[-1] * 0.97), False))
     worst = 0.0
     n_cand_seen = 0
     for name, st, sp, n_in, want_lazy in cases:
