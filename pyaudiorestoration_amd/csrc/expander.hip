@@ -102,6 +102,8 @@ __global__ void __launch_bounds__(256) k_expand_gain(const float* __restrict__ s
     double g;
     if (j >= frames - 1) {
       g = fac[frames - 1 - j0];                                     // at and past the last frame: its value (np.interp's right)
+    } else if (i == j * hop) {
+      g = fac[j - j0];                                              // on a frame: its value, as np.interp -- a NaN neighbour stays out
     } else {
       const double slope = (fac[j + 1 - j0] - fac[j - j0]) / (double)hop;
       g = slope * ((double)i - (double)(j * hop)) + fac[j - j0];

@@ -18,6 +18,7 @@
 //
 // Built with -ffp-contract=off: the mask's a*a + b*b and S x mask round every step separately, as numpy does.
 #include "par_common.h"
+#include "np_abs.h"
 #include <math.h>
 #include <cmath>
 
@@ -39,19 +40,6 @@ struct HpssParams {
   int pow_mode, out_kind;
   float power, margin_h, margin_p, bad_value;
 };
-
-// numpy's complex64 absolute (stft.hip gate_mag without the renoiser's + 1e-7): larger * sqrt(fma(r, r, 1)), r = smaller / larger,
-// every step a correctly rounded float32 operation.  The division and sqrtf are the compiler's correctly rounded expansions
-// (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn is NOT: without OCML_BASIC_ROUNDED_OPERATIONS the
-// header maps it to the native v_sqrt_f32, an ulp off in one bin of eight.
-__device__ __forceinline__ float np_abs_c64(float re, float im) {
-  const float ar = fabsf(re), ai = fabsf(im);
-  if (ar == __builtin_inff() || ai == __builtin_inff()) return __builtin_inff();
-  if (ar != ar || ai != ai) return __builtin_nanf("");
-  const float larger = fmaxf(ar, ai), smaller = fminf(ar, ai);
-  const float r = larger == 0.0f ? 0.0f : smaller / larger;
-  return sqrtf(fmaf(r, r, 1.0f)) * larger;
-}
 
 // scipy's "reflect" (half-sample symmetric, d c b a | a b c d | d c b a), repeated as often as the halo needs.  Only positions
 // off the axis pay for the 64-bit remainder: those are the halos of the tiles at an edge.

@@ -17,6 +17,7 @@
 // each output bin is written once; magnitude never round-trips a complex spectrogram.
 #include "par_common.h"
 #include "db_math.h"
+#include "np_abs.h"
 #include <math.h>
 #include <map>
 #include <set>
@@ -1230,18 +1231,12 @@ static inline bool istft_is_fused(int n_fft, int hop) {
 // get_mask_fac: a bin passes unchanged when float32(20 log10(float32(|X| + 1e-7))) > final[k], else it is multiplied by the
 // float32 factor 10^(gain/20).  float32 20 log10 is monotone, so the host turns each threshold into one float32 magnitude
 // cutoff c[k] (renoiser.gate_cutoffs): "passes" is then |X| + 1e-7 >= c[k] -- no transcendental per bin, and a NaN cutoff
-// gates every bin.  |X| is the float32 value numpy's np.abs gives for complex64, which its SIMD loop computes as
-// larger * sqrt(fma(r, r, 1)), r = smaller / larger, every step a correctly rounded float32 operation (not hypotf: that
-// differs from numpy in about a quarter of all bins by an ulp, and v_sqrt_f32 of mode 1 by another).  Contraction off: the
-// product and the + 1e-7 round separately, as numpy's do.
+// gates every bin.  |X| is the float32 value numpy's np.abs gives for complex64 (np_abs.h: correctly rounded division and
+// square root; the native v_sqrt_f32 this function used before gated 12.8 % of the bins that sit exactly on their cutoff).
+// Contraction off: the product and the + 1e-7 round separately, as numpy's do.
 __device__ __forceinline__ float gate_mag(float re, float im) {
 #pragma clang fp contract(off)
-  const float ar = fabsf(re), ai = fabsf(im);
-  if (ar == __builtin_inff() || ai == __builtin_inff()) return __builtin_inff();
-  if (ar != ar || ai != ai) return __builtin_nanf("");
-  const float larger = fmaxf(ar, ai), smaller = fminf(ar, ai);
-  const float r = larger == 0.0f ? 0.0f : __fdiv_rn(smaller, larger);
-  const float mag = __fsqrt_rn(fmaf(r, r, 1.0f)) * larger;
+  const float mag = np_abs_c64(re, im);
   return mag + 1e-7f;
 }
 // X * fac as numpy multiplies complex64 by a float32 (fac becomes fac + 0i): the products with the zero imaginary part are kept
@@ -1282,11 +1277,15 @@ struct GateGeom {
   static size_t lds(int hop) {
     return (size_t)G::Frames * G::FrameLds * sizeof(float2) + (size_t)(ring(hop) + hop) * sizeof(float);
   }
+  // Waves per SIMD the register allocation must keep (the second __launch_bounds__ argument).  The 2048- and 8192-point kernels
+  // sit at 168 VGPRs, the last count at which three waves fit; the correctly rounded square root of gate_mag took them to 169 and
+  // 171, two waves, and 2048/512 from 1.31 to 1.69 ms.  The other sizes state what they had.
+  static constexpr int kWaves = LOGH == 3 ? 7 : (LOGH == 11 ? 2 : 3);
 };
 
 template <int LOGH>
-__global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_gate_stft(const float* __restrict__ x, int64_t n, int64_t x_stride,
-                                                                      int hop, int s, int rounds, int ring,
+__global__ __launch_bounds__(FftGeom<LOGH>::Threads, GateGeom<LOGH>::kWaves) void k_gate_stft(const float* __restrict__ x, int64_t n,
+                                                                      int64_t x_stride, int hop, int s, int rounds, int ring,
                                                                       const float* __restrict__ window, const float2* __restrict__ tw,
                                                                       const float2* __restrict__ post, const float* __restrict__ cutoff,
                                                                       float low, float* __restrict__ y, int64_t y_stride,
