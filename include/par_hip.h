@@ -5,7 +5,7 @@
  * HBM (the Python host layer allocates it through torch-ROCm tensors); `stream`
  * is a hipStream_t passed as void* (NULL = the default stream).  The library keeps
  * no global state except small per-device constant tables (twiddles, sinc tap
- * tables) keyed by (device, size).
+ * tables, the fixed-ratio resampler's filter table) keyed by (device, size).
  *
  * All functions return an int status (0 = PAR_OK), never throw, and record a
  * message retrievable with par_last_error() (thread-local).  Functions are
@@ -517,6 +517,23 @@ int par_hpss_f32(int device, const void* spec, int is_complex, int64_t n_frames,
  * hpss_gui.py:145 on channel views of interleaved signals). */
 int par_residual_f32(int device, const float* x, int64_t x_stride, const float* h, int64_t h_stride, const float* p,
                      int64_t p_stride, int64_t n, float* r, int64_t r_stride, void* stream);
+
+/* ---- fixed-ratio resampling (resampy.resample(x, sr_orig, sr_new, axis=0, filter='sinc_window', num_zeros=Z)) --------------------
+ * par_resample_fixed_out_len and par_resample_fixed_f32 are added at ABI 109: par_version() stays 109. */
+/* Samples the resampler writes for n input samples: int(n * sr_new / sr_orig), evaluated left to right in double (host only;
+ * -1 for a negative n or rates that are not finite and positive). */
+int64_t par_resample_fixed_out_len(int64_t n, double sr_orig, double sr_new);
+/* y[t * y_stride], t < n_out, = Smith's band-limited interpolation of x[i * x_stride], i < n (DEVICE f32, channel views of
+ * interleaved arrays; x and y distinct buffers) at the positions t * (1 / ratio), ratio = sr_new / sr_orig, over resampy
+ * 0.4's interpolated 'sinc_window' table: 512 entries per zero crossing, rolloff 0.945, symmetric Hann taper, linear
+ * interpolation between entries, table step int(min(1, ratio) * 512), the sum scaled by ratio when ratio < 1.  Positions,
+ * table offsets and interpolation fractions are float64 and equal numpy's bit for bit; weights and sums are float32.  The
+ * wings are cut at the signal's ends (no padding): nothing outside x[0, n) is read, no other cell of y is written.
+ * n_out must be par_resample_fixed_out_len(n, sr_orig, sr_new).  Null pointers, rates that are not finite and positive,
+ * num_zeros outside 1..64, strides < 1, a wrong n_out and x == y: PAR_ERR_ARG before any device call; n == 0 or n_out == 0:
+ * PAR_OK, nothing done; ratio outside [1/16, 16]: PAR_ERR_UNSUPPORTED.  The table is built once per (device, num_zeros). */
+int par_resample_fixed_f32(int device, const float* x, int64_t n, int64_t x_stride, double sr_orig, double sr_new, int num_zeros,
+                           float* y, int64_t n_out, int64_t y_stride, void* stream);
 #ifdef __cplusplus
 }
 #endif

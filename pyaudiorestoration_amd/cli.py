@@ -13,6 +13,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli expand --channels L+R --clip -120,-85 tape.wav     # Spectral Expander -> tape_decompressed.wav
     python -m pyaudiorestoration_amd.cli renoise --noise hiss.wav tape.wav                  # renoiser -> "tape fft=2048.wav"
     python -m pyaudiorestoration_amd.cli hpss --kernel 31,17 --margin 2,3 take.flac         # -> take_H.wav, take_P.wav, take_R.wav
+    python -m pyaudiorestoration_amd.cli humspeed --hum 50 --resample tape.wav              # -> tape_resampled_<percent>.wav
 """
 import argparse
 import json
@@ -30,7 +31,7 @@ def _worker(dev, jobs, args, results):
     release the GIL) on a helper thread while the current one is on the GPU."""
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    from . import _dev, expander, hpss, io_ops, pipeline, renoiser, resampling
+    from . import _dev, expander, hpss, humspeed, io_ops, pipeline, renoiser, resampling
     torch.cuda.set_device(dev)
 
     def take():
@@ -38,7 +39,7 @@ def _worker(dev, jobs, args, results):
             path = jobs.get_nowait()
         except queue.Empty:
             return None
-        if args.cmd in ("tapesync", "heal") or (args.cmd == "respeed" and args.project):        # these flows read their source themselves
+        if args.cmd in ("tapesync", "heal", "humspeed") or (args.cmd == "respeed" and args.project):   # these flows read their source themselves
             return path, None
         return path, reader.submit(io_ops.read_file, path)
 
@@ -56,6 +57,16 @@ def _worker(dev, jobs, args, results):
                         flow(args.project, source=path, out_suffix=args.suffix, device=dev)
                     results.append((path, None))
                     continue
+                if args.cmd == "humspeed":
+                    res = humspeed.analyse(path, args.channels, args.hum, args.harmonies, args.tolerance, args.fft)
+                    for f, db, ratio in zip(res["marker_freqs"], res["marker_dBs"], res["ratios"]):
+                        logging.info("%s: marker %.4f Hz %.2f dB, Percent Change: %.3f", path, f, db, (ratio - 1) * 100)
+                    if not res["ratios"]:
+                        logging.warning("%s: hum was not close enough", path)
+                    elif args.resample:                 # the last ratio, like the GUI's Resample button
+                        logging.info("%s: wrote %s", path, humspeed.resample_file(path, res["ratios"][-1], device=dev))
+                    results.append((path, None))
+                    continue
                 signal, sr, ch = pending.result()
                 if args.cmd == "expand":
                     expander.expand_file(path, args.channels, args.fft_size, args.hop, args.band[0], args.band[1], args.smoothing,
@@ -65,7 +76,7 @@ def _worker(dev, jobs, args, results):
                     continue
                 if args.cmd == "renoise":
                     renoiser.renoise_file(path, args.noise, args.select, args.fft, args.overlap, args.gain, args.overhead, args.curve,
-                                          args.channels, device=dev, signal_data=(signal, sr, ch))
+                                          args.channels, device=dev, signal_data=(signal, sr, ch), resample_noise=args.resample_noise)
                     results.append((path, None))
                     continue
                 if args.cmd == "hpss":
@@ -139,6 +150,7 @@ def parser():
     r = sub.add_parser("renoise", help="renoiser: gate (or boost) every STFT bin at or under a noise profile + gain + overhead")
     prof = r.add_mutually_exclusive_group()
     prof.add_argument("--noise", default=None, help="noise recording at the file's sample rate (its first channel is the profile)")
+    r.add_argument("--resample-noise", action="store_true", help="resample a noise recording at another rate to the file's (default: refuse it)")
     prof.add_argument("--select", type=pair, default=None, help="T0,T1 (s): the profile is this time range of channel 0")
     r.add_argument("--fft", type=int, default=2048, help="FFT size")
     r.add_argument("--overlap", type=int, default=4, help="hop = fft / overlap")
@@ -164,6 +176,15 @@ def parser():
     h.add_argument("--margin", type=one_or_two(float), default=1.0, help="mask margin(s) >= 1; other than 1 also writes the residual")
     h.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
     h.add_argument("files", nargs="+")
+    m = sub.add_parser("humspeed", help="hum speed analysis: how far the mains hum is off its nominal frequency; --resample corrects it")
+    m.add_argument("--channels", default="L+R", choices=("L+R", "L", "R"), help="which channels are analysed")
+    m.add_argument("--hum", type=int, default=50, help="base frequency of the hum (Hz)")
+    m.add_argument("--harmonies", type=int, default=2, help="number of hum harmonics to consider")
+    m.add_argument("--tolerance", type=int, default=8, help="largest deviation from a hum frequency (percent)")
+    m.add_argument("--fft", type=int, default=524288, help="FFT size of the averaged spectrum")
+    m.add_argument("--resample", action="store_true", help="write <stem>_resampled_<percent>.wav, corrected by the last ratio")
+    m.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
+    m.add_argument("files", nargs="+")
     return ap
 
 

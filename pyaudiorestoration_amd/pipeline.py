@@ -529,13 +529,17 @@ def lag_curve_from_markers(markers, duration, sr, hop, smoothing=3, bands=(0, 99
     return np.stack((times, filters.butter_bandpass_filter(lag_at(times), lo, hi, marker_sr, order=3)), axis=-1)
 
 
-def correlate_sources(ref_sig, src_sig, sr, lower, upper, ignore_phase=False, window_name=None, speed=1.0):
+def correlate_sources(ref_sig, src_sig, sr, lower, upper, ignore_phase=False, window_name=None, speed=1.0, match_speed=False):
     """Delay (seconds) and correlation between two signal windows, as the tape-sync tool measures them
     (pytapesynch_gui.py:108-133 behind its widget lookups): both windows band-passed (order-3 zero-phase Butterworth,
     K_sosfiltfilt), then find_delay -- filter outputs stay in HBM and feed the correlation there.  `speed`: the rough
-    speed difference the caller resampled `src_sig` by (its match_speed branch uses resampy, not part of this
-    package); the delay is corrected for it like the reference does.  The inputs are not modified."""
-    from . import correlation, filters
+    speed difference between the sources; the delay is corrected for it like the reference does.  match_speed=False: the
+    caller has already resampled `src_sig` by it; match_speed=True is the reference's match_speed branch
+    (pytapesynch_gui.py:117-122): `src_sig` is first resampled with fixed_rate.resample(src_sig, sr / speed, sr), where the
+    reference calls resampy.  The inputs are not modified."""
+    from . import correlation, filters, fixed_rate
+    if match_speed:
+        src_sig = fixed_rate.resample(src_sig, sr / speed, sr, axis=0, filter='sinc_window', num_zeros=8)
     a_t = filters.bandpass_dev(ref_sig, lower, upper, sr, order=3)
     b_t = filters.bandpass_dev(src_sig, lower, upper, sr, order=3)
     if window_name:                                  # find_delay windows in place: never the caller's own buffers

@@ -15,9 +15,9 @@ become one float32 magnitude cutoff per bin on the host (gate_cutoffs), so the k
 same spectrum.
 
 Differences from the reference:
-- Noise at another sample rate raises ValueError.  The GUI first passes it through resampy's sinc_window resampler
-  (num_zeros=8); the profile is taken from the samples as given when the rates are equal, which is also what
-  experiments/renoiser.py does then.
+- Noise at another sample rate raises ValueError unless resample_noise=True asks for the GUI's pass through the sinc_window
+  resampler (num_zeros=8), which is fixed_rate.resample here (float32 sums, resampy computes in the file's dtype); the profile
+  is taken from the samples as given when the rates are equal, which is also what experiments/renoiser.py does then.
 - An empty selection (no frame between t0 and t1) raises ValueError; the reference would produce a NaN profile.
 - The input is never modified.  Repeated channel numbers raise ValueError (the reference leaves the columns they skip
   uninitialised); a channel number at or above the number of selected channels raises IndexError, as the reference's
@@ -30,7 +30,7 @@ import os
 import numpy as np
 import torch
 
-from . import _dev, _lib, fourier, io_ops, spectrum_flat
+from . import _dev, _lib, fixed_rate, fourier, io_ops, spectrum_flat
 
 WINDOW = "blackmanharris"
 # GUI defaults (util/widgets.py:768-810, 326-351): FFT 2048, overlap 4, gain 12 dB, overhead 3 dB, zero padding forced to 1
@@ -53,12 +53,18 @@ def default_profile(sr, fft_size=FFT_SIZE):
     return np.full(len(fourier.fft_freqs(fft_size, sr)), NO_PROFILE_DB, dtype=np.float32)
 
 
-def noise_profile(noise, noise_sr, sr, fft_size=FFT_SIZE, hop=FFT_SIZE // OVERLAP, device=None):
+def noise_profile(noise, noise_sr, sr, fft_size=FFT_SIZE, hop=FFT_SIZE // OVERLAP, device=None, resample_noise=False):
     """Mean decibel spectrum of the first channel of a noise recording, float64 (bins,) like the reference's numpy STFT backend
-    makes it -- load_noise_profile.  The noise must be at the signal's rate (ValueError otherwise: there is no resampy pass)."""
-    if int(noise_sr) != int(sr):
-        raise ValueError(f"noise sample rate {noise_sr} != signal rate {sr}: resample the noise first (no resampy pass here)")
+    makes it -- load_noise_profile.  Noise at another rate than the signal's: ValueError by default; with resample_noise=True
+    it is first resampled to the signal's rate, fixed_rate.resample(noise, noise_sr, sr), as the GUI does with resampy."""
+    if int(noise_sr) != int(sr) and not resample_noise:
+        raise ValueError(f"noise sample rate {noise_sr} != signal rate {sr}: resample the noise first (no resampy pass here; "
+                         "resample_noise=True runs fixed_rate.resample)")
     dev = _dev.device_index(device if device is not None else (noise.device if torch.is_tensor(noise) else None))
+    if int(noise_sr) != int(sr):
+        # channels are independent and only the first is read below
+        noise = fixed_rate.resample(_dev.to_dev(_as_2d(noise)[:, 0], torch.float32, dev), noise_sr, sr, axis=0,
+                                    filter='sinc_window', num_zeros=8, device=dev)
     n2d = _as_2d(noise)
     n, ch = n2d.shape
     flat = _dev.to_dev(n2d, torch.float32, dev).reshape(-1)
@@ -215,9 +221,9 @@ def output_path(path, fft_size):
 
 
 def renoise_file(path, noise_path=None, selection=None, fft_size=FFT_SIZE, overlap=OVERLAP, gain=GAIN, overhead=OVERHEAD,
-                 curve=None, channels=None, device=None, signal_data=None):
+                 curve=None, channels=None, device=None, signal_data=None, resample_noise=False):
     """The GUI's flow on a file: read `path` (signal_data=(signal, sr, channels) skips the read); the noise profile comes from
-    the noise file `noise_path` (same rate), from the time range selection=(t0, t1) of channel 0, or is the -100 dB default;
+    the noise file `noise_path` (same rate, or any rate with resample_noise=True), from the time range selection=(t0, t1) of channel 0, or is the -100 dB default;
     apply and write "<stem> fft=<N>.wav" (float32 WAV).  Returns the written path, or None when no channel is selected (the
     reference then writes nothing)."""
     if noise_path is not None and selection is not None:
@@ -231,7 +237,7 @@ def renoise_file(path, noise_path=None, selection=None, fft_size=FFT_SIZE, overl
     sig_t = _dev.to_dev(_as_2d(signal), torch.float32, dev).contiguous()
     if noise_path is not None:
         noise, noise_sr, _ = io_ops.read_file(noise_path)
-        prof = noise_profile(noise, noise_sr, sr, fft_size, hop, dev)
+        prof = noise_profile(noise, noise_sr, sr, fft_size, hop, dev, resample_noise=resample_noise)
     elif selection is not None:
         prof = noise_profile_from_selection(sig_t, sr, selection[0], selection[1], fft_size, hop, 0, dev)
     else:
