@@ -381,12 +381,18 @@ int par_track_corr_f64(int device, const float* mag, int64_t n_frames, int bins,
 /* X2: util/correlation.py:6-39 on the device.  a, b: float64 device signals (what butter_bandpass_filter hands to
  * find_delay, pytapesynch_gui.py:128-131).
  *   par_xcorr_f64       scipy.signal.correlate(a/|a|, b/|b|, 'full'): full[na + nb - 1] float64, through one complex
- *                       float32 transform of a + i b (values carry ~1e-6 of the peak)
+ *                       float32 transform of a/|a| + i b/|b| (values carry ~1e-6; measured per transform size, and with
+ *                       takes 80 dB apart in level, in tests/test_xcorr_gpu.py)
  *   par_find_delay_f64  find_delay(a, b, ignore_phase) with the window already applied by the caller (the reference
  *                       multiplies a and b in place): the peak of the 'same' correlation is located by the transform,
  *                       the lags around it are re-evaluated as float64 dot products and parabolic() (:42-46) runs on
  *                       those; *delay = peak - na//2 (host), *corr = its height.  A peak on the last lag is the
  *                       reference's IndexError: PAR_ERR_INDEX.  Synchronises.
+ *                       Rival peaks: every local maximum of the transform's output within kXcRivalTol = 4.0e-6 of its
+ *                       top, more than two lags from it, is re-evaluated exactly and the exact values decide (lowest
+ *                       lag on a tie).  The exact argmax is certain to be listed while twice the transform's worst
+ *                       error stays below kXcRivalTol.  Up to 63 rivals are decided; 64 or more are taken for a
+ *                       plateau and the transform's own top stands.
  *   scratch             device bytes of par_xcorr_scratch_bytes(na, nb).  na + nb - 1 <= 2^20: one transform; longer signals
  *                       (up to 2^25 samples each, else PAR_ERR_UNSUPPORTED) are correlated in pairs of 2^19-sample sections */
 size_t par_xcorr_scratch_bytes(int64_t na, int64_t nb);

@@ -780,14 +780,16 @@ __global__ __launch_bounds__(256) void k_huge_out(const float2* __restrict__ Zr,
 // ---- X2: normalised cross-correlation and delay search (util/correlation.py:6-39) ---------------------------
 // scipy.signal.correlate(a/|a|, b/|b|, 'full') through ONE complex transform of z = a + i b (both zero-padded to
 // N >= len a + len b - 1): A_k = (Z_k + conj Z_{N-k})/2, B_k = (Z_k - conj Z_{N-k})/(2i), cross spectrum A conj(B),
-// inverse transform by the conjugate trick.  The float32 transform places the peak (error ~1e-6 of it); find_delay
+// inverse transform by the conjugate trick.  z is packed from the NORMALISED signals: each half of Z_k carries the float32
+// rounding of the whole of z, so with the raw signals a take 40 dB below the other one came out 100 times less exact
+// (tests/test_xcorr_gpu.py, unequal levels).  The float32 transform places the peak (error ~1e-6 of it); find_delay
 // then re-evaluates the few lags around it as float64 dot products, so the parabola through the peak -- the delay
 // the tape-sync tool uses -- is exact.
 __global__ __launch_bounds__(256) void k_xc_pack(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
-                                                 int64_t nb, float2* __restrict__ Z, int64_t N) {
+                                                 int64_t nb, const double* __restrict__ norms, float2* __restrict__ Z, int64_t N) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  Z[i] = make_float2(i < na ? (float)a[i] : 0.0f, i < nb ? (float)b[i] : 0.0f);
+  Z[i] = make_float2(i < na ? (float)(a[i] / norms[0]) : 0.0f, i < nb ? (float)(b[i] / norms[1]) : 0.0f);
 }
 // conj(A_k conj(B_k)) for the second (forward) transform
 __global__ __launch_bounds__(256) void k_xc_cross(const float2* __restrict__ Z, float2* __restrict__ C, int64_t N) {
@@ -800,19 +802,19 @@ __global__ __launch_bounds__(256) void k_xc_cross(const float2* __restrict__ Z, 
   const float2 c = cmul(A, cconj(B));
   C[k] = cconj(c);
 }
-// full[j] = circ[(j - (nb-1)) mod N] / (N |a| |b|), j = 0 .. na + nb - 2
+// full[j] = circ[(j - (nb-1)) mod N] / N, j = 0 .. na + nb - 2 (the signals went in normalised)
 __global__ __launch_bounds__(256) void k_xc_unpack(const float2* __restrict__ Y, int64_t N, int64_t nb, int64_t n_full,
-                                                   const double* __restrict__ norms, double* __restrict__ full) {
+                                                   double* __restrict__ full) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= n_full) return;
-  full[j] = (double)Y[(j - (nb - 1)) & (N - 1)].x / ((double)N * norms[0] * norms[1]);
+  full[j] = (double)Y[(j - (nb - 1)) & (N - 1)].x / (double)N;
 }
-// sectioned form: full[j] += circ[(j - (nbq-1)) mod N] / (N |a| |b|) for the n_local lags of one section pair
+// sectioned form: full[j] += circ[(j - (nbq-1)) mod N] / N for the n_local lags of one section pair
 __global__ __launch_bounds__(256) void k_xc_unpack_acc(const float2* __restrict__ Y, int64_t N, int64_t nbq, int64_t n_local,
-                                                       const double* __restrict__ norms, double* __restrict__ full) {
+                                                       double* __restrict__ full) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= n_local) return;
-  full[j] += (double)Y[(j - (nbq - 1)) & (N - 1)].x / ((double)N * norms[0] * norms[1]);
+  full[j] += (double)Y[(j - (nbq - 1)) & (N - 1)].x / (double)N;
 }
 // norms[0] = |a|, norms[1] = |b| (float64, one workgroup each)
 __global__ __launch_bounds__(1024) void k_xc_norms(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
@@ -862,6 +864,10 @@ __global__ __launch_bounds__(1024) void k_xc_argmax(const double* __restrict__ v
   if (threadIdx.x == 0) *arg = bi[0];
 }
 constexpr int kXcCand = 64;                        // rival peaks find_delay re-evaluates exactly
+// Listing tolerance: a rival is listed when the transform puts it within kXcRivalTol of the transform's top.  With e the
+// transform's worst error, a rival whose exact value reaches the exact top reads at least top - 2e, so 2e <= kXcRivalTol
+// lists it for certain (include/par_hip.h; measured per transform size in tests/test_xcorr_gpu.py, NOTES.md "Correlation").
+constexpr double kXcRivalTol = 4.0e-6;
 // Rival peaks: the float32 transform finds the peak to ~1e-6 of its height; a periodic tone, or the +/- lobes
 // under ignore_phase, can put another local maximum within that distance of the top more than two lags away, and the
 // reference's float64 argmax may pick that one.  Every local maximum (of |v| under use_abs) within `tol` of the
@@ -1755,7 +1761,8 @@ static int xcorr_full(int device, const double* a, int64_t na, const double* b, 
       const int64_t la = na - pa < kXcSection ? na - pa : kXcSection;
       for (int64_t qb = 0; qb < nb; qb += kXcSection) {
         const int64_t lb = nb - qb < kXcSection ? nb - qb : kXcSection;
-        hipLaunchKernelGGL(k_xc_pack, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, a + pa, la, b + qb, lb, Z, N);
+        hipLaunchKernelGGL(k_xc_pack, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, a + pa, la, b + qb, lb,
+                           (const double*)norms, Z, N);
         int rc = big_fft_c2c(device, Z, Y, N, 1, s);
         if (rc != PAR_OK) return rc;
         hipLaunchKernelGGL(k_xc_cross, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, (const float2*)Y, Z, N);
@@ -1764,21 +1771,21 @@ static int xcorr_full(int device, const double* a, int64_t na, const double* b, 
         // local index jl = lag + lb - 1; global index = lag + (pa - qb) + nb - 1
         const int64_t joff = pa - qb + nb - lb;
         hipLaunchKernelGGL(k_xc_unpack_acc, dim3((unsigned)ceil_div(la + lb - 1, 256)), dim3(256), 0, s, (const float2*)Y, N, lb,
-                           la + lb - 1, (const double*)norms, full + joff);
+                           la + lb - 1, full + joff);
       }
     }
     PAR_HIP_CHECK(hipGetLastError());
     *norms_out = norms;
     return PAR_OK;
   }
-  hipLaunchKernelGGL(k_xc_pack, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, a, na, b, nb, Z, N);
+  hipLaunchKernelGGL(k_xc_pack, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, a, na, b, nb, (const double*)norms, Z, N);
   int rc = big_fft_c2c(device, Z, Y, N, 1, s);                       // Y = FFT(a + i b)
   if (rc != PAR_OK) return rc;
   hipLaunchKernelGGL(k_xc_cross, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, (const float2*)Y, Z, N);
   rc = big_fft_c2c(device, Z, Y, N, 1, s);                           // Y = conj(N * circular correlation)
   if (rc != PAR_OK) return rc;
   hipLaunchKernelGGL(k_xc_unpack, dim3((unsigned)ceil_div(na + nb - 1, 256)), dim3(256), 0, s, (const float2*)Y, N, nb,
-                     na + nb - 1, (const double*)norms, full);
+                     na + nb - 1, full);
   PAR_HIP_CHECK(hipGetLastError());
   *norms_out = norms;
   return PAR_OK;
@@ -1821,7 +1828,8 @@ int par_find_delay_f64(int device, const double* a, int64_t na, const double* b,
     double* cvals = vals + 8 + kXcCand;
     int* n_cand = reinterpret_cast<int*>(cvals + kXcCand);
     PAR_HIP_CHECK(hipMemsetAsync(n_cand, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_xc_candidates, dim3(1), dim3(1024), 0, s, same, na, ignore_phase, (const long long*)arg, 4.0e-6, cand, n_cand);
+    hipLaunchKernelGGL(k_xc_candidates, dim3(1), dim3(1024), 0, s, same, na, ignore_phase, (const long long*)arg, kXcRivalTol, cand,
+                       n_cand);
     int nc = 0;
     long long top = 0;
     PAR_HIP_CHECK(hipMemcpyAsync(&nc, n_cand, sizeof(int), hipMemcpyDeviceToHost, s));
