@@ -540,6 +540,26 @@ int64_t par_resample_fixed_out_len(int64_t n, double sr_orig, double sr_new);
  * PAR_OK, nothing done; ratio outside [1/16, 16]: PAR_ERR_UNSUPPORTED.  The table is built once per (device, num_zeros). */
 int par_resample_fixed_f32(int device, const float* x, int64_t n, int64_t x_stride, double sr_orig, double sr_new, int num_zeros,
                            float* y, int64_t n_out, int64_t y_stride, void* stream);
+/* ---- renoiser "Gauge offset" (renoiser_gui.py:347-369 sniff_offset, experiments/renoiser.py:59-73) -----------------------------
+ * par_gauge_frames, par_gauge_scratch_bytes and par_gauge_offset_f32 are added at ABI 109: par_version() stays 109. */
+/* Frames of the reference's STFT for pad `offset`: (n + offset + n_fft/2) / hop + 1 (host only; -1 for n < 0, n_fft < 2,
+ * hop < 1 or a negative offset). */
+int64_t par_gauge_frames(int64_t n, int n_fft, int hop, int offset);
+/* Bytes of DEVICE scratch par_gauge_offset_f32 needs (host only; 0 for arguments it refuses): three float64 sums per dense
+ * workgroup and residue slot, and one complex64 per pad and edge frame. */
+size_t par_gauge_scratch_bytes(int64_t n, int n_fft, int hop);
+/* stds[i], i < hop (DEVICE f64) = the standard deviation over the frames (numpy's std of a complex array, ddof 0) of
+ *   z(i, j) = sum_m p_i[j hop + m] (h_re[m] + 1j h_im[m]),   m = 0 .. n_fft - 1,   j < par_gauge_frames(n, n_fft, hop, i)
+ * where p_i is x[k * x_stride], k < n (DEVICE f32, a channel view of an interleaved signal) with i zeros in front, zero-extended
+ * by n_fft/2 and reflect-padded by n_fft/2 at both ends as par_stft_f32 pads: with M = n + i + n_fft/2, padded index q maps to
+ * r = q - n_fft/2, r < 0 to -r, r >= M to 2 (M - 1) - r, value x[r - i] for i <= r < i + n, else 0.  With h (DEVICE f32
+ * [n_fft] each part) = renoiser.gauge_filter, z is the mean of bins l..u-1 of the reference's STFT and stds its curve.  Each
+ * part of z is one float32 FMA chain over ascending m; sum z, sum |z|^2 are float64 in a fixed order (no atomics: two runs are
+ * bit-identical); std = sqrt(max(0, sum|z|^2 / F - |sum z / F|^2)), NaN kept.  Any n_fft >= 2 and hop >= 1.  Nothing but
+ * stds[0 .. hop) and scratch is written.  Null pointers, n < 1, n_fft < 2, hop < 1, x_stride < 1, scratch_bytes below
+ * par_gauge_scratch_bytes (or a scratch that is not 8-byte aligned): PAR_ERR_ARG before any device call. */
+int par_gauge_offset_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, const float* h_re,
+                         const float* h_im, double* stds, void* scratch, size_t scratch_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

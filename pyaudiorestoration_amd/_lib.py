@@ -116,6 +116,9 @@ SIGNATURES = {
     "par_residual_f32": (c_int, [c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "par_resample_fixed_out_len": (c_i64, [c_i64, c_dbl, c_dbl]),
     "par_resample_fixed_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_dbl, c_dbl, c_int, c_vp, c_i64, c_i64, c_vp]),
+    "par_gauge_frames": (c_i64, [c_i64, c_int, c_int, c_int]),
+    "par_gauge_scratch_bytes": (c_sz, [c_i64, c_int, c_int]),
+    "par_gauge_offset_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 HPSS_COMPONENTS, HPSS_MASKS, HPSS_HARMONIC, HPSS_MEDIANS = 0, 1, 2, 3      # par_hpss_f32's out_kind (PAR_HPSS_*)
 NORMALIZE_SCRATCH_BYTES = 4096      # PAR_NORMALIZE_SCRATCH_BYTES

@@ -3,7 +3,7 @@
 Each csrc/*.hip is compiled to an object with per-file flags, then linked.  pos.hip (float64
 positions that must be bit-identical to numpy), resample_fixed.hip (float64 positions and table offsets likewise), expander.hip (numpy's interpolation, compensated sums) and hpss.hip (numpy's
 float32 soft mask) are built with -ffp-contract=off; the other kernels
-keep hipcc's default contraction and spell their FMAs explicitly."""
+keep hipcc's default contraction and spell their FMAs explicitly (gauge.hip among them: every tap is an fmaf)."""
 import glob
 import os
 import subprocess
@@ -22,6 +22,7 @@ PER_FILE = {"pos.hip": ["-ffp-contract=off"],
             # SLP packing into v_pk_*_f32 buys no throughput on gfx950 and costs v_mov shuffles
             "sinc.hip": ["-fno-slp-vectorize"],
             "sinc2.hip": ["-fno-slp-vectorize"],
+            "gauge.hip": ["-fno-slp-vectorize"],      # K_gauge's tap loop is 256 v_fma per 16 taps; packed, half of them plus v_mov shuffles
             "stft.hip": ["-fno-slp-vectorize"]}
 
 

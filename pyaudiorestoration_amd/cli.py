@@ -12,6 +12,8 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli heal --project tape.drop tape.flac
     python -m pyaudiorestoration_amd.cli expand --channels L+R --clip -120,-85 tape.wav     # Spectral Expander -> tape_decompressed.wav
     python -m pyaudiorestoration_amd.cli renoise --noise hiss.wav tape.wav                  # renoiser -> "tape fft=2048.wav"
+    python -m pyaudiorestoration_amd.cli renoise --gauge tape.wav                           # "Gauge offset": logs the best pad
+    python -m pyaudiorestoration_amd.cli renoise --noise hiss.wav --offset auto tape.wav    # ... and applies with it
     python -m pyaudiorestoration_amd.cli hpss --kernel 31,17 --margin 2,3 take.flac         # -> take_H.wav, take_P.wav, take_R.wav
     python -m pyaudiorestoration_amd.cli humspeed --hum 50 --resample tape.wav              # -> tape_resampled_<percent>.wav
 """
@@ -74,9 +76,15 @@ def _worker(dev, jobs, args, results):
                                          signal_data=(signal, sr, ch))
                     results.append((path, None))
                     continue
+                if args.cmd == "renoise" and args.gauge:        # "Gauge offset" on channel 0: no audio is written
+                    _, stds, pad = renoiser.sniff_offset(signal, sr, args.fft, args.fft // args.overlap, 0, device=dev)
+                    logging.info("%s: gauge maximum %.9g at pad %d of %d", path, stds[pad], pad, len(stds))
+                    results.append((path, None))
+                    continue
                 if args.cmd == "renoise":
                     renoiser.renoise_file(path, args.noise, args.select, args.fft, args.overlap, args.gain, args.overhead, args.curve,
-                                          args.channels, device=dev, signal_data=(signal, sr, ch), resample_noise=args.resample_noise)
+                                          args.channels, device=dev, signal_data=(signal, sr, ch), resample_noise=args.resample_noise,
+                                          offset=args.offset)
                     results.append((path, None))
                     continue
                 if args.cmd == "hpss":
@@ -158,6 +166,9 @@ def parser():
     r.add_argument("--overhead", type=float, default=3.0, help="dB added to the profile")
     r.add_argument("--curve", type=curve, default=None, help="F:DB,... control curve (default 1:0,<sr/2>:0)")
     r.add_argument("--channels", type=ints, default=None, help="channel numbers, e.g. 0,1 (default: all)")
+    r.add_argument("--gauge", action="store_true", help="only gauge the frame offset of an earlier denoise on channel 0 and log it")
+    r.add_argument("--offset", type=lambda s: s if s == "auto" else int(s), default=0,
+                   help="zeros in front of the signal before the STFT, 0 <= K < hop, or 'auto' for the gauged pad")
     r.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
     r.add_argument("files", nargs="+")
 
