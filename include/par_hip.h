@@ -175,7 +175,8 @@ int par_speed_to_pos_plan_ex(int device, const double* sampletimes, const double
 /* Why this thread's most recent plan left the device path: the device scans' flag word (1 near-tie in the segment
  * lengths, 2 some n_i < 2, 4 a_i outside the exact fixed-point range, 8 offset-chain verification failed, 16 more
  * binade crossings than the stitch table holds, 64 end_guess within the device sum's error of an integer); 0 when the
- * plan ran on the device (path_used 0) or the host path was forced.  Diagnostics only. */
+ * plan ran on the device (path_used 0; 64 alone is settled on the side and leaves the plan there) or the host path was
+ * forced.  Diagnostics only. */
 int par_last_plan_flags(void);
 int par_speed_to_pos_fill(int device, const double* speeds, int64_t m, const void* work,
                           double* pos, int64_t len_out, void* stream);

@@ -65,7 +65,16 @@ __global__ __launch_bounds__(256) void k_lerp(const double* __restrict__ pos, in
     } else {
       const double y0 = (double)sig[i * sig_stride], y1 = (double)sig[(i + 1) * sig_stride];
       // numpy's interp kernel: slope*(x - x0) + y0 with slope = (y1-y0)/(x1-x0), x1-x0 == 1
-      v = (float)((y1 - y0) * (p - (double)i) + y0);   // separate roundings: this file is built with -ffp-contract=off
+      const double slope = y1 - y0;
+      double r = y0;                                   // x == xp[j] returns fp[j] (an inf or NaN neighbour never enters)
+      if (p != (double)i) {
+        r = slope * (p - (double)i) + y0;              // separate roundings: this file is built with -ffp-contract=off
+        if (isnan(r)) {                                // numpy's retry from the right knot, as interp_one above
+          r = slope * (p - (double)(i + 1)) + y1;
+          if (isnan(r) && y0 == y1) r = y0;
+        }
+      }
+      v = (float)r;
     }
   }
   out[j * out_stride] = v;

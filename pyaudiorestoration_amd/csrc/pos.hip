@@ -2143,6 +2143,9 @@ static int host_plan(const PlanView& pv, const double* d_st, const double* d_sp,
   out->done_tile_seg_publish = 0;
   out->written = acc;
   out->first_bad = kNoTrim;
+  out->lazy = 0;            // (`out` arrives holding the header of the device go that sent the plan here, a lazy one perhaps)
+  out->lazy_fail = 0;
+  out->n_cand = 0;
   PAR_HIP_CHECK(hipMemcpyAsync(pv.seg_start, start.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, s));
   PAR_HIP_CHECK(hipMemcpyAsync(pv.seg_off, off.data(), m * sizeof(double), hipMemcpyHostToDevice, s));
   PAR_HIP_CHECK(hipMemcpyAsync(pv.hdr, out, sizeof(PlanHeader), hipMemcpyHostToDevice, s));
@@ -2378,6 +2381,7 @@ static int plan_impl(int device, const double* sampletimes, const double* speeds
     } else if (h.n_long > 0 && !go.with_long) {
       go.with_long = true;                      // sparse curve: once more, with the chunked exact cumsum of its long segments
     } else {
+      g_last_plan_flags |= h.flags;             // (before the 64 is settled: par_last_plan_flags reports it, include/par_hip.h)
       if (h.flags & kFlagCapAmbiguous) {
         // Only the buffer bound is in doubt: settle int(mean * span * 1.01) with numpy's own pairwise order on the host
         // (one D2H of the speed samples); everything else the device computed stands.
@@ -2392,7 +2396,6 @@ static int plan_impl(int device, const double* sampletimes, const double* speeds
         PAR_HIP_CHECK(hipMemcpyAsync(pv.hdr, &h, sizeof(h), hipMemcpyHostToDevice, s));
         PAR_HIP_CHECK(hipStreamSynchronize(s));
       }
-      g_last_plan_flags |= h.flags;
       if (h.flags == 0) break;                  // done
       // a near-tie in the lengths alone: once more, with host-made lengths; anything else (n_i < 2, range, verification,
       // too many crossings, or a second failure): the serial path decides -- it also produces the reference's own

@@ -97,6 +97,7 @@ def oracle_spot(out_t, pos, sig_t, NT, windows=5, width=1200, sig_stride=1, tol=
         p = pos[i:i + width + 1]
         finite = np.isfinite(p)
         lo = int(max(0, np.floor(np.min(p[finite])) - 200)) if finite.any() else 0
+        lo -= lo & 1               # even: a position exactly ON k + 1/2 keeps the window centre rint() gives it (ties go to even)
         hi = int(min(len(sig), np.ceil(np.max(p[finite])) + 200)) if finite.any() else len(sig)
         if lo == 0 or hi - lo > 4_000_000 or lo > len(sig) - 4096:      # (window-local coordinates only where they are safe and pay:
             # the leading edge and windows at or beyond the signal's end -- an empty or clipped slice -- keep absolute ones)

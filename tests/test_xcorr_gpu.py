@@ -248,6 +248,19 @@ def test_linear_resample_equals_np_interp(C, n, lo):
     assert got.dtype == np.float32 and len(diff) == 0, (diff[:5], pos[diff[:5]], got[diff[:5]], want[diff[:5]])
 
 
+@pytest.mark.parametrize("name", sorted(X.lerp_nonfinite()))
+def test_linear_resample_beside_samples_that_are_not_finite(C, name):
+    """np.interp's two branches beside the slope formula: x == xp[j] returns fp[j] (slope * 0 would make NaN of an inf neighbour, and
+    +0.0 of a sample that is -0.0), and a NaN result is tried again from the right knot -- equal as uint32, a NaN's payload aside"""
+    import torch
+    from pyaudiorestoration_amd import resampling
+    sig, pos = X.lerp_nonfinite()[name]
+    want = X.lerp_oracle(pos, sig)
+    got = resampling.linear_resample_dev(torch.from_numpy(pos).cuda(), torch.from_numpy(sig).cuda()).cpu().numpy()
+    same = (bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))
+    assert got.dtype == np.float32 and same.all(), (pos[~same], got[~same], want[~same])
+
+
 def test_linear_resample_strided_channel_between_sentinels(C):
     """channel 1 of an interleaved stereo buffer into channel 1 of an interleaved output: the other channel's cells and the cells
     around the output keep their sentinel bit for bit, and the poisoned input channel is never read into a result"""

@@ -164,5 +164,27 @@ def test_interp_inputs():
     assert all(float(t * sr).is_integer() for t in c[:, 0])
 
 
+def test_interp_inputs_beside_samples_that_are_not_finite():
+    """np.interp on the signals of lerp_nonfinite gives the values written out below, and the bare slope formula -- what a kernel without
+    np.interp's x == xp[j] branch and its retry from the right knot computes -- differs from it at every position the inputs exist for"""
+    sig, pos = X.lerp_nonfinite()["inf_and_nan"]
+    want = X.lerp_oracle(pos, sig)
+    table = {0.0: 1.0, 1.0: np.inf, 1.5: np.inf, 2.0: np.inf, 3.0: 2.0, 0.5: np.inf, 2.5: np.inf, 5.0: 3.0, 5.5: 3.5, 6.0: 4.0}
+    for x, y in table.items():
+        assert np.all(want[pos == x] == y), (x, y, want[pos == x])                 # (pos == 0.0 holds for -0.0 too)
+    assert np.signbit(pos[1]) and np.isnan(want[(pos > 3.0) & (pos < 5.0)]).all() and np.isfinite(want[pos >= 5.0]).all()
+
+    def bare(pos, sig):
+        i = np.minimum(np.floor(pos).astype(np.int64), len(sig) - 2)
+        y0, y1 = sig[i].astype(np.float64), sig[i + 1].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            return ((y1 - y0) * (pos - i) + y0).astype(np.float32)
+    for name, at in (("inf_and_nan", [0.0, 1.0, 1.5, 2.0, 2.5, 3.0]), ("minus_inf", [0.0, 2.0, 3.0, 3.5, 4.0]), ("signed_zero", [0.0, 2.0, 3.0])):
+        sig, pos = X.lerp_nonfinite()[name]
+        want, plain = X.lerp_oracle(pos, sig), bare(pos, sig)
+        differ = (want.view(np.uint32) != plain.view(np.uint32)) & ~(np.isnan(want) & np.isnan(plain))
+        assert set(at) <= set(pos[differ]), (name, pos[differ])
+
+
 def test_zz_run_time():
     print(f"\ntests/test_xcorr_inputs_cpu.py: {time.perf_counter() - T0:.1f} s since import")

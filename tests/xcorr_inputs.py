@@ -266,6 +266,19 @@ def lerp_positions(n, lo, count, seed=0):
     return pos
 
 
+def lerp_nonfinite():
+    """{name: (float32 signal, positions)}: samples that are not finite, as a float WAV can hold them, read ON them and between
+    them -- np.interp returns fp[j] where x == xp[j] and retries from the right knot where the left one gives NaN, so a neighbour that
+    is inf or NaN reaches only the outputs strictly inside its two intervals -- and negative zeros read on them"""
+    inf, nan = np.inf, np.nan
+    return {
+        "inf_and_nan": (np.array([1, inf, inf, 2, nan, 3, 4], np.float32),
+                        np.array([0.0, -0.0, 0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 3.5, 4.0, 4.5, 5.0, 5.25, 5.5, 5.75, 6.0])),
+        "minus_inf": (np.array([-inf, 0, inf, -inf, -inf, 7], np.float32), np.arange(0.0, 5.01, 0.25)),
+        "signed_zero": (np.array([-0.0, 1, -0.0, -0.0, 2, 0.0, -3], np.float32), np.arange(0.0, 6.01, 0.5)),
+    }
+
+
 def lag_curves():
     """{name: (lag curve (m, 2) in seconds, sr, len_signal)}"""
     sr = 48000
