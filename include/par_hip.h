@@ -561,6 +561,52 @@ size_t par_gauge_scratch_bytes(int64_t n, int n_fft, int hop);
  * par_gauge_scratch_bytes (or a scratch that is not 8-byte aligned): PAR_ERR_ARG before any device call. */
 int par_gauge_offset_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, const float* h_re,
                          const float* h_im, double* stds, void* scratch, size_t scratch_bytes, void* stream);
+/* ---- dynamics matcher (experiments/decompressor_cmd.py:26-188 process, after its band-pass) -----------------------------------
+ * par_windowed_rms_log10_f64, par_level_match_f64, par_uniform_filter_reflect_f64, par_dynamics_factor_f64 and
+ * par_dynamics_apply_f32 are added at ABI 109: par_version() stays 109.  All work on the caller's stream, none synchronises the
+ * host, none needs scratch; fixed summation orders, no atomics: two runs are bit-identical. */
+/* out[r * F + j], j < F = ceil(n / hop) (DEVICE f64) = the windowed RMS of decompressor_cmd.py:16-23 of row r of x (DEVICE
+ * f64[rows][x_pitch], n samples used):
+ *   rms = sqrt(sum of x[i]^2 over j hop <= i < min(j hop + sz, n), divided by the number of those samples)
+ * -- the last windows are truncated and their mean divides by the truncated length -- then np.clip(rms, floor, None) (a NaN
+ * stays) and, for log10_out != 0, log10 of it (:93-96 with floor 0.0005; a clipped frame stores the host libm's log10(floor));
+ * log10_out == 0 stores the clipped RMS itself (floor 0: the plain RMS, exactly 0 for a silent window).  Any hop >= 1 and sz >= 1 (sz % hop != 0, sz < hop, sz > n).  Squares and
+ * sums are float64: per hop-aligned piece a fixed order over the lanes, then the pieces of a frame ascending; at most sz + 1
+ * roundings bear on a sum.  Every sample is read once per 1024 frames (+ sz samples).  Null pointers, rows outside 1..65535,
+ * n, hop or sz < 1, x_pitch < n, a NaN floor: PAR_ERR_ARG before any device call. */
+int par_windowed_rms_log10_f64(int device, const double* x, int64_t x_pitch, int64_t rows, int64_t n, int hop, int sz, double floor,
+                               int log10_out, double* out, void* stream);
+/* out_b[r * F + j] = (b[r * F + j] - mean(b[r])) + mean(a[r]), r < rows, j < F (DEVICE f64; decompressor_cmd.py:97, in its
+ * order).  Each mean is a float64 sum in a fixed two-level order (1024 strided runs, ascending, then a tree over them) divided
+ * by F.  out_b may be b itself, not a.  Null pointers, rows or F < 1: PAR_ERR_ARG before any device call. */
+int par_level_match_f64(int device, const double* a, const double* b, int64_t rows, int64_t F, double* out_b, void* stream);
+/* scipy.ndimage.uniform_filter1d(in[r], size) -- the default mode "reflect" (d c b a | a b c d | d c b a), origin 0 -- for each
+ * of `rows` rows of n float64 (DEVICE, row-major, out != in): out[i] = mean of the extended row over
+ * [i - size / 2, i + size - size / 2 - 1]; size >= 1 of either parity, rows shorter than the window reflect repeatedly
+ * (position q reads m = q mod 2n, or 2n - 1 - m for m >= n).  Compensated window sums as par_uniform_filter_nearest_f64:
+ * within about an ulp of the exact window mean; size 1 returns the input bit for bit (decompressor_cmd.py:99-100). */
+int par_uniform_filter_reflect_f64(int device, const double* in, int64_t rows, int64_t n, int size, double* out, void* stream);
+/* Steps :109-166 for rows r < rows of F frames (DEVICE f64 a = the source's smoothed log curve, b = the reference's), with
+ * ch = corr_sz / 2, K = (F - 1) / ch, k = i / ch + 1, m = i % ch and hann (DEVICE f64[corr_sz]) = np.hanning(corr_sz), computed
+ * by the host (no cosine is evaluated on the device):
+ *   aligned[i] = 0.0 (+ a[i] * hann[m + ch] if k <= K) (+ a[i] * hann[m] if k + 1 <= K)     two products, added in this order
+ *   fac[i]     = nan_to_num(clip(10^b[i] / 10^aligned[i], 0, 2))                               a NaN becomes 0
+ * which is the reference's Hann overlap-add of the edge-padded curve with do_sync False, bit for bit -- including its tail:
+ * frames from (K - 1) ch on carry the falling half of the window only, frames from K ch - 1 on (all of them for F <= ch) are 0,
+ * so fac = min(10^b, 2) there.  aligned_or_null: when not NULL, receives aligned (f64[rows][F]).  corr_sz odd or < 2, null
+ * pointers, rows outside 1..65535, F < 1: PAR_ERR_ARG before any device call. */
+int par_dynamics_factor_f64(int device, const double* a, const double* b, int64_t rows, int64_t F, const double* hann, int corr_sz,
+                            double* aligned_or_null, double* fac, void* stream);
+/* Steps :169-185 on the interleaved signal sig[i * sig_stride + c], c < n_ch, i < n (DEVICE f32) with fac (DEVICE
+ * f64[n_ch][F], F = ceil(n / hop), frame j at sample j hop):
+ *   g_c  = np.interp(i, j hop, fac[c]): fac[c][j] on a key, (fac[c][j+1] - fac[c][j]) / hop * (i - j hop) + fac[c][j] between
+ *          two, fac[c][F-1] from the last key on
+ *   g    = np.mean over the channels: the left-to-right sum g_0 + g_1 + .. divided by n_ch
+ *   out[i * out_stride + c] = float32(float64(sig) * g)        one rounding to float32
+ * Equals numpy on the same fac bit for bit.  n_ch > 8: PAR_ERR_UNSUPPORTED.  Null pointers, n, hop or n_ch < 1, a stride below
+ * n_ch, F != ceil(n / hop), out == sig: PAR_ERR_ARG before any device call. */
+int par_dynamics_apply_f32(int device, const float* sig, int64_t sig_stride, int n_ch, int64_t n, const double* fac, int64_t F,
+                           int hop, float* out, int64_t out_stride, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Builds libpar_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 Each csrc/*.hip is compiled to an object with per-file flags, then linked.  pos.hip (float64
-positions that must be bit-identical to numpy), resample_fixed.hip (float64 positions and table offsets likewise), expander.hip (numpy's interpolation, compensated sums) and hpss.hip (numpy's
+positions that must be bit-identical to numpy), resample_fixed.hip (float64 positions and table offsets likewise), expander.hip and dynamics.hip (numpy's interpolation, compensated sums) and hpss.hip (numpy's
 float32 soft mask) are built with -ffp-contract=off; the other kernels
 keep hipcc's default contraction and spell their FMAs explicitly (gauge.hip among them: every tap is an fmaf)."""
 import glob
@@ -19,6 +19,7 @@ PER_FILE = {"pos.hip": ["-ffp-contract=off"],
             "expander.hip": ["-ffp-contract=off"],
             "hpss.hip": ["-ffp-contract=off"],
             "resample_fixed.hip": ["-ffp-contract=off"],
+            "dynamics.hip": ["-ffp-contract=off"],    # numpy's overlap-add and interpolation, rounding by rounding
             # SLP packing into v_pk_*_f32 buys no throughput on gfx950 and costs v_mov shuffles
             "sinc.hip": ["-fno-slp-vectorize"],
             "sinc2.hip": ["-fno-slp-vectorize"],

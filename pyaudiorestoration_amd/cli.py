@@ -16,6 +16,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli renoise --noise hiss.wav --offset auto tape.wav    # ... and applies with it
     python -m pyaudiorestoration_amd.cli hpss --kernel 31,17 --margin 2,3 take.flac         # -> take_H.wav, take_P.wav, take_R.wav
     python -m pyaudiorestoration_amd.cli humspeed --hum 50 --resample tape.wav              # -> tape_resampled_<percent>.wav
+    python -m pyaudiorestoration_amd.cli dynamics remaster.flac original.flac               # -> remaster.flacdecompressed.wav
 """
 import argparse
 import json
@@ -196,6 +197,9 @@ def parser():
     m.add_argument("--resample", action="store_true", help="write <stem>_resampled_<percent>.wav, corrected by the last ratio")
     m.add_argument("--gpus", type=int, default=0, help="GPUs to use (0 = all visible)")
     m.add_argument("files", nargs="+")
+    y = sub.add_parser("dynamics", help="dynamics matcher (decompressor_cmd): restore SRC's dynamics to those of REF -> SRC + 'decompressed.wav'")
+    y.add_argument("src", metavar="SRC", help="the transfer to restore")
+    y.add_argument("ref", metavar="REF", help="a transfer of the same recording with the intended dynamics (same length, rate and channels)")
     return ap
 
 
@@ -205,6 +209,10 @@ def main(argv=None):
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no ROCm GPU visible; this tool has no CPU fallback")
+    if args.cmd == "dynamics":                  # one pair of files, one GPU
+        from . import decompressor
+        logging.info("wrote %s", decompressor.process(args.src, args.ref))
+        return 0
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()
     for f in sorted(args.files, key=lambda p: -os.path.getsize(p)):     # longest first

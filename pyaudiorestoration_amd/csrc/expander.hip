@@ -2,7 +2,7 @@
 //
 //   k_mean_db_frames  spectrum_flat.py:20-24: to_dB of a magnitude block, summed over its frames per bin (the temporal mean's
 //                     numerator; the caller divides by the frame count once all chunks are in)
-//   k_uniform_nearest expander_gui.py:134: scipy.ndimage.uniform_filter1d(v, size, mode="nearest") along rows
+//   k_uniform<kEdgeNearest> (uniform_filter.h) expander_gui.py:134: scipy.ndimage.uniform_filter1d(v, size, mode="nearest") along rows
 //   k_expand_gain     expander_gui.py:184-197: clip -> to_fac -> np.interp onto the samples -> signal x factor
 //   k_sum_rows        expander_gui.py:201: lp + hp (float64) stored into the float32 (n, ch) signal
 //   k_absmax / k_div  util/units.py:32-39 normalize: d /= max|d|
@@ -12,6 +12,7 @@
 // compensated sums rely on every rounding step being a separate one.
 #include "par_common.h"
 #include "db_math.h"
+#include "uniform_filter.h"
 #include <math.h>
 
 namespace par {
@@ -36,41 +37,6 @@ __global__ void __launch_bounds__(kMeanBins * kMeanLanes) k_mean_db_frames(const
 #pragma unroll
     for (int l = 1; l < kMeanLanes; ++l) t += part[l][bl];
     acc[b] += t;
-  }
-}
-
-// Neumaier's compensated running sum: the window sum of every output is exact to about an ulp whatever the window length
-// (a plain running sum drifts with the number of slides)
-struct CompSum {
-  double s = 0.0, c = 0.0;
-  __device__ __forceinline__ void add(double v) {
-    const double t = s + v;
-    c += (fabs(s) >= fabs(v)) ? (s - t) + v : (v - t) + s;
-    s = t;
-  }
-  __device__ __forceinline__ double value() const { return s + c; }
-};
-
-// One thread per segment of `seg` outputs of one row: the window sum of the segment's first output is taken directly,
-// then the window slides (one sample in, one out).  seg >= size keeps the direct sum at most half of a thread's work.
-__global__ void __launch_bounds__(256) k_uniform_nearest(const double* __restrict__ in, int64_t n, int size, int64_t seg,
-                                                         int64_t n_seg, double* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_seg) return;
-  const int64_t row = blockIdx.y;
-  const double* x = in + row * n;
-  double* y = out + row * n;
-  const int64_t h = size / 2;
-  const int64_t i0 = t * seg, i1 = (i0 + seg < n) ? i0 + seg : n;
-  auto at = [&](int64_t q) { return x[q < 0 ? 0 : (q >= n ? n - 1 : q)]; };      // mode "nearest": the edge values repeat
-  CompSum acc;
-  for (int64_t q = i0 - h; q <= i0 + h; ++q) acc.add(at(q));
-  const double inv = (double)size;
-  y[i0] = acc.value() / inv;
-  for (int64_t i = i0 + 1; i < i1; ++i) {
-    acc.add(at(i + h));
-    acc.add(-at(i - h - 1));
-    y[i] = acc.value() / inv;
   }
 }
 
@@ -198,7 +164,7 @@ extern "C" int par_uniform_filter_nearest_f64(int device, const double* in, int6
   const int64_t seg = size > 256 ? size : 256;
   const int64_t n_seg = ceil_div(n, seg);
   PAR_HIP_CHECK(hipSetDevice(device));
-  hipLaunchKernelGGL(k_uniform_nearest, dim3((unsigned)ceil_div(n_seg, 256), (unsigned)rows), dim3(256), 0, as_stream(stream), in, n, size,
+  hipLaunchKernelGGL(k_uniform<kEdgeNearest>, dim3((unsigned)ceil_div(n_seg, 256), (unsigned)rows), dim3(256), 0, as_stream(stream), in, n, size,
                      seg, n_seg, out);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
