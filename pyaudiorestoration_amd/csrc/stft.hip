@@ -1161,8 +1161,12 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) __attribute__((amdgpu_waves
   // 16-term loop PER SAMPLE (they were a third of the kernel's instructions at 512/32).
   float* env_tab = wl + n_fft;          // kTab: behind the window (pl is dead now); else behind the staged window in the frame slots
   const bool use_tab = kTab || n_fft + hop <= 2 * G::Frames * G::FrameLds;
+  // hop > n_fft leaves a gap of hop - n_fft samples behind every frame (phases >= n_fft) that no frame covers: the table has no
+  // entry for them (it holds min(hop, n_fft) sums, which is what the LDS behind the window has room for) and the store loop
+  // below writes their zero without touching the window, the table or the accumulator, whose last frame ends at its n_fft.
+  const int tab_len = hop < n_fft ? hop : n_fft;
   if (use_tab) {
-    for (int ph = tid; ph < hop; ph += G::Threads) {
+    for (int ph = tid; ph < tab_len; ph += G::Threads) {
       float env = 0.0f;
       for (int o = ph + ((n_fft - 1 - ph) / hop) * hop; o >= 0; o -= hop) env += wl[o] * wl[o];
       env_tab[ph] = env;
@@ -1177,7 +1181,7 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) __attribute__((amdgpu_waves
     if (t < 0) continue;
     if (t >= y_len) break;
     float a = 0.0f;
-    if (TT < ola_len) {
+    if (TT < ola_len && ph < n_fft) {                                  // (ph >= n_fft: a gap sample, see the table above)
       float env;
       if (use_tab && TT >= interior_lo && TT <= interior_hi) {
         env = env_tab[ph];
@@ -1894,9 +1898,11 @@ int par_istft_f32(int device, const float* spec, int64_t n_frames, int n_fft, in
   PAR_REQUIRE(n_frames >= 1 && hop >= 1 && y_len >= 0 && skip >= 0, PAR_ERR_ARG, "par_istft_f32: bad sizes");
   PAR_REQUIRE(n_fft >= 16 && n_fft <= (1 << 21) && (n_fft & (n_fft - 1)) == 0, PAR_ERR_UNSUPPORTED,
               "par_istft_f32: n_fft=%d is not a power of two in [16, 2^21]", n_fft);
+  // (before any HIP call, like the other argument errors: a caller without the scratch hears so on any machine)
+  PAR_REQUIRE(frames || (n_fft <= 8192 && istft_is_fused(n_fft, hop)), PAR_ERR_ARG,
+              "par_istft_f32: n_fft=%d hop=%d needs the frames scratch (par_istft_scratch_floats)", n_fft, hop);
   PAR_HIP_CHECK(hipSetDevice(device));
   if (n_fft > 8192) {                              // frames of the four-step size class (the GUI's FFT sizes go to 2^20)
-    PAR_REQUIRE(frames, PAR_ERR_ARG, "par_istft_f32: n_fft=%d needs the scratch of par_istft_scratch_floats", n_fft);
     const int64_t H = n_fft / 2, B = istft_big_batch(n_frames, n_fft);
     float2* A = reinterpret_cast<float2*>(frames + ((n_frames * (int64_t)n_fft + 3) & ~3ll));
     float2* V = A + B * H;
@@ -1952,7 +1958,6 @@ int par_istft_f32(int device, const float* spec, int64_t n_frames, int n_fft, in
     PAR_HIP_CHECK(hipGetLastError());
     return PAR_OK;
   }
-  PAR_REQUIRE(frames, PAR_ERR_ARG, "par_istft_f32: n_fft=%d hop=%d needs the frames scratch (par_istft_scratch_floats)", n_fft, hop);
 #define PAR_ISTFT_LAUNCH(LH)                                                                                            \
   hipLaunchKernelGGL(k_istft_frames<LH>, dim3((unsigned)ceil_div(n_frames, FftGeom<LH>::Frames)),                         \
                      dim3(FftGeom<LH>::Threads), (size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2),      \
