@@ -402,6 +402,46 @@ int par_xcorr_f64(int device, const double* a, int64_t na, const double* b, int6
 int par_find_delay_f64(int device, const double* a, int64_t na, const double* b, int64_t nb, int ignore_phase, void* scratch,
                        size_t scratch_bytes, double* delay, double* corr, void* stream);
 
+/* X2 batch: the tape-sync tool's azimuth mode (pytapesynch_gui.py:210-238) cuts, filters and correlates one window pair per
+ * dur/overlap seconds of a selection.  par_find_delay_batch_f64 and par_gather_windows_f64 are added at ABI 109:
+ * par_version() stays 109.
+ *   par_find_delay_batch_f64  find_delay for n_win pairs of rows of one shape: a DEVICE f64 [n_win][a_pitch] (na used),
+ *                       b DEVICE f64 [n_win][b_pitch] (nb used).  win_a [na] / win_b [nb]: DEVICE f64 or NULL; when given,
+ *                       every row is multiplied by its window IN PLACE first (util/correlation.py:18-20), so after the
+ *                       call the rows hold row * win.  delay, corr: DEVICE f64 [n_win]; status: DEVICE int32 [n_win],
+ *                       0 = ok, 1 = the peak sits on lag na - 1 (the reference's IndexError in parabolic()): delay and
+ *                       corr of THAT row are NaN, every other row is computed.  A row of zeros has norm 0: delay and corr
+ *                       are NaN with status 0, as the reference's division carries it.
+ *                       The work per window is par_find_delay_f64's -- norms, one packed float32 transform pair, first
+ *                       argmax, rivals within kXcRivalTol re-decided exactly (64 or more: the transform's top stands),
+ *                       exact values at peak-3 .. peak+3, numpy's f[-1] wrap at peak 0, parabolic() -- decided on the
+ *                       device: nothing is copied to the host and the call does not synchronise (a device's first
+ *                       call of a transform size uploads its twiddles).  Every value that enters (delay, corr) is the
+ *                       float64 sum par_find_delay_f64 forms, in its order: row by row the results are its results.
+ *                       na + nb - 1 <= 2^20 (one transform per window), else PAR_ERR_UNSUPPORTED: loop over
+ *                       par_find_delay_f64.  na < 3, nb < 1, n_win < 0, a pitch below its length, a null pointer:
+ *                       PAR_ERR_ARG before any device call.  n_win == 0: PAR_OK, nothing done.
+ *   scratch             DEVICE bytes.  par_find_delay_batch_scratch_bytes gives the size for all n_win windows in one pass,
+ *                       capped at 32768 windows and at 1 GiB of transform arrays plus the per-window tables, never less than
+ *                       one window's worth (0: the shape is unsupported).  Any size from one window's worth up is accepted
+ *                       (less: PAR_ERR_WORKSPACE); the windows go through in passes of as many as it holds and the results
+ *                       do not depend on it.
+ *   par_gather_windows_f64  Spectrum.get_signal (util/spectrum.py:158-171) for n_win windows of one channel:
+ *                       out[w * out_pitch + i] = (double)sig[(starts[w] + i - pad_l[w]) * sig_stride] for
+ *                       pad_l[w] <= i < pad_l[w] + lens[w], 0.0 for every other i < n_out; nothing at i >= n_out.
+ *                       sig: DEVICE f32, sample k of the channel at sig[k * sig_stride], n samples.  starts, lens, pad_l:
+ *                       DEVICE int64 [n_win].  host_geom: HOST int64 [3][n_win] = the same starts, lens and pad_l rows, one
+ *                       after the other; the call checks THESE before anything is launched: a window with a negative
+ *                       field, starts + lens > n or pad_l + lens > n_out is PAR_ERR_ARG.  The kernel itself reads nothing
+ *                       outside sig[0, n) whatever the device arrays hold. */
+size_t par_find_delay_batch_scratch_bytes(int64_t na, int64_t nb, int64_t n_win);
+int par_find_delay_batch_f64(int device, double* a, int64_t a_pitch, int64_t na, double* b, int64_t b_pitch, int64_t nb,
+                             int64_t n_win, const double* win_a, const double* win_b, int ignore_phase, void* scratch,
+                             size_t scratch_bytes, double* delay, double* corr, int32_t* status, void* stream);
+int par_gather_windows_f64(int device, const float* sig, int64_t sig_stride, int64_t n, const int64_t* starts, const int64_t* lens,
+                           const int64_t* pad_l, const int64_t* host_geom, int64_t n_win, int64_t n_out, double* out,
+                           int64_t out_pitch, void* stream);
+
 /* W3: sign-change indices of a (band-passed) float64 signal, ascending -- zero_crossings(a) =
  * np.where(np.bitwise_xor(a[1:] > 0, a[:-1] > 0))[0] (util/wow_detection.py:448-450), the full-rate pass of
  * ZeroCrossingTracker.trace (:340).

@@ -17,6 +17,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli hpss --kernel 31,17 --margin 2,3 take.flac         # -> take_H.wav, take_P.wav, take_R.wav
     python -m pyaudiorestoration_amd.cli humspeed --hum 50 --resample tape.wav              # -> tape_resampled_<percent>.wav
     python -m pyaudiorestoration_amd.cli dynamics remaster.flac original.flac               # -> remaster.flacdecompressed.wav
+    python -m pyaudiorestoration_amd.cli azimuth take.tapesync --ref take1.flac --box 12,300,22,3000 --out take2.tapesync
 """
 import argparse
 import json
@@ -200,6 +201,16 @@ def parser():
     y = sub.add_parser("dynamics", help="dynamics matcher (decompressor_cmd): restore SRC's dynamics to those of REF -> SRC + 'decompressed.wav'")
     y.add_argument("src", metavar="SRC", help="the transfer to restore")
     y.add_argument("ref", metavar="REF", help="a transfer of the same recording with the intended dynamics (same length, rate and channels)")
+    z = sub.add_parser("azimuth", help="tape-sync azimuth mode: measure one azimuth line of a pytapesynch project (.tapesync)")
+    z.add_argument("project", metavar="PROJECT", help=".tapesync JSON written by the GUI")
+    z.add_argument("--ref", required=True, help="the reference file")
+    z.add_argument("--src", default=None, help="the file to synchronise (default: the project's source)")
+    z.add_argument("--box", required=True, type=pair, help="T0,F0,T1,F1 (s, Hz): the selection in the reference's spectrogram")
+    z.add_argument("--win", type=float, default=0.2, help="half window (s)")
+    z.add_argument("--overlap", type=int, default=32, help="windows per half window")
+    z.add_argument("--reject", type=float, default=0.1, help="lags whose |correlation| is below this are interpolated over")
+    z.add_argument("--ignore-phase", action="store_true", help="correlate on |.|")
+    z.add_argument("--out", default=None, metavar="PROJECT2", help="write the project with the line appended (default: only log)")
     return ap
 
 
@@ -212,6 +223,15 @@ def main(argv=None):
     if args.cmd == "dynamics":                  # one pair of files, one GPU
         from . import decompressor
         logging.info("wrote %s", decompressor.process(args.src, args.ref))
+        return 0
+    if args.cmd == "azimuth":                   # one pair of files, one GPU
+        from . import pipeline
+        if len(args.box) != 4:
+            raise SystemExit("--box takes T0,F0,T1,F1")
+        pipeline.measure_azimuth(args.project, args.ref, args.src, args.box, args.win, args.overlap, args.reject, args.ignore_phase,
+                                 args.out)
+        if args.out:
+            logging.info("wrote %s", args.out)
         return 0
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()

@@ -82,3 +82,66 @@ def find_delay(a, b, ignore_phase=False, window_name=None):
                                     ctypes.byref(delay), ctypes.byref(corr), _dev.stream_ptr(dev)))
     logging.debug(f"i_peak {delay.value + na // 2}")
     return delay.value, corr.value
+
+
+def batch_scratch_bytes(na, nb, n_win):
+    """Device bytes par_find_delay_batch_f64 asks for to take all windows in one pass; raises ParUnsupported for a shape
+    the batch does not take (na + nb - 1 > 2^20: the sectioned form)."""
+    L = _lib.lib()
+    nbytes = int(L.par_find_delay_batch_scratch_bytes(na, nb, n_win))
+    if nbytes == 0:
+        raise _lib.ParUnsupported(3, f"find_delay_batch: windows of {na} and {nb} samples need the sectioned form (or are empty)")
+    return nbytes
+
+
+def find_delay_batch_dev(a_t, b_t, ignore_phase=False, window_name=None, dev=None, scratch_bytes=None):
+    """find_delay for every pair of rows of two 2-D float64 device tensors (W, na) and (W, nb) (row stride >= row length,
+    unit element stride) in one call: -> (delays, corrs, status) device tensors of length W, status 1 where the peak sits
+    on the last lag (the reference's IndexError; that row's delay and corr are NaN).  A given window is applied to the
+    rows IN PLACE, like find_delay.  Raises nothing for a row's status; scratch_bytes: device bytes for the passes
+    (default: what the library asks for)."""
+    dev = _dev.device_index(dev if dev is not None else a_t.device)
+    if a_t.ndim != 2 or b_t.ndim != 2 or a_t.shape[0] != b_t.shape[0]:
+        raise ValueError("find_delay_batch needs (W, na) and (W, nb)")
+    W, na = a_t.shape
+    nb = b_t.shape[1]
+    if a_t.dtype != torch.float64 or b_t.dtype != torch.float64 or (W and (a_t.stride(1) != 1 or b_t.stride(1) != 1)):
+        raise ValueError("find_delay_batch_dev needs float64 rows of unit element stride")
+    L = _lib.lib()
+    delays = _dev.empty(W, torch.float64, dev)
+    corrs = _dev.empty(W, torch.float64, dev)
+    status = _dev.empty(W, torch.int32, dev)
+    if W == 0:
+        return delays, corrs, status
+    nbytes = batch_scratch_bytes(na, nb, W) if scratch_bytes is None else int(scratch_bytes)
+    scratch = _dev.empty(max(nbytes, 1), torch.uint8, dev)
+    win_a = win_b = None
+    if window_name:
+        win_a = _dev.to_dev(get_window(window_name, na), torch.float64, dev)
+        win_b = _dev.to_dev(get_window(window_name, nb), torch.float64, dev)
+    _lib.check(L.par_find_delay_batch_f64(dev, _dev.ptr(a_t), a_t.stride(0) if W > 1 else max(a_t.stride(0), na), na, _dev.ptr(b_t),
+                                          b_t.stride(0) if W > 1 else max(b_t.stride(0), nb), nb, W,
+                                          _dev.ptr(win_a) if window_name else None, _dev.ptr(win_b) if window_name else None,
+                                          int(bool(ignore_phase)), _dev.ptr(scratch), nbytes, _dev.ptr(delays), _dev.ptr(corrs),
+                                          _dev.ptr(status), _dev.stream_ptr(dev)))
+    return delays, corrs, status
+
+
+def find_delay_batch(a, b, ignore_phase=False, window_name=None):
+    """find_delay(a[w], b[w]) for every row w of a (W, na) and b (W, nb), numpy or float64 device tensors -> (delays, corrs),
+    float64 numpy arrays of length W.  Like find_delay, a given window is applied to `a` and `b` IN PLACE.  The first row
+    whose peak sits on the last lag raises the reference's IndexError, with the row's index."""
+    if ignore_phase:
+        logging.warning("Ignoring phase")
+    dev = _dev.device_index(None)
+    a_t, b_t = (s if isinstance(s, torch.Tensor) else _dev.to_dev(np.asarray(s), torch.float64, dev) for s in (a, b))
+    delays, corrs, status = find_delay_batch_dev(a_t, b_t, ignore_phase, window_name, dev)
+    for host, t in ((a, a_t), (b, b_t)):
+        if window_name and not isinstance(host, torch.Tensor):      # the in-place contract for host arrays
+            host[...] = _dev.to_host(t)
+    status = status.cpu().numpy()
+    bad = np.flatnonzero(status == 1)
+    if len(bad):
+        na = a_t.shape[1]
+        raise IndexError(f"index {na} is out of bounds for axis 0 with size {na} (row {int(bad[0])})")
+    return _dev.to_host(delays), _dev.to_host(corrs)

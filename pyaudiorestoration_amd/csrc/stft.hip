@@ -816,23 +816,28 @@ __global__ __launch_bounds__(256) void k_xc_unpack_acc(const float2* __restrict_
   if (j >= n_local) return;
   full[j] += (double)Y[(j - (nbq - 1)) & (N - 1)].x / (double)N;
 }
-// norms[0] = |a|, norms[1] = |b| (float64, one workgroup each)
-__global__ __launch_bounds__(1024) void k_xc_norms(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
-                                                   int64_t nb, double* __restrict__ norms) {
-  __shared__ double part[16];
-  const double* v = blockIdx.x ? b : a;
-  const int64_t n = blockIdx.x ? nb : na;
+// |v| in float64 by one 1024-thread workgroup (valid in thread 0): THE summation order of the norm, shared by the single
+// and the batched delay search so that both divide by the same bits
+__device__ inline double xc_norm_1024(const double* __restrict__ v, int64_t n, double* part /* LDS [16] */) {
   double acc = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 1024) acc += v[i] * v[i];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
+  double t = 0.0;
   if (threadIdx.x == 0) {
-    double t = 0.0;
     for (int w = 0; w < 16; ++w) t += part[w];
-    norms[blockIdx.x] = sqrt(t);
+    t = sqrt(t);
   }
+  return t;
+}
+// norms[0] = |a|, norms[1] = |b| (float64, one workgroup each)
+__global__ __launch_bounds__(1024) void k_xc_norms(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
+                                                   int64_t nb, double* __restrict__ norms) {
+  __shared__ double part[16];
+  const double t = xc_norm_1024(blockIdx.x ? b : a, blockIdx.x ? nb : na, part);
+  if (threadIdx.x == 0) norms[blockIdx.x] = t;
 }
 // first index of the maximum of v[lo .. lo+n) (|v| when ignore_phase), one workgroup
 __global__ __launch_bounds__(1024) void k_xc_argmax(const double* __restrict__ v, int64_t n, int use_abs, long long* __restrict__ arg) {
@@ -889,46 +894,237 @@ __global__ __launch_bounds__(1024) void k_xc_candidates(const double* __restrict
     }
   }
 }
+// exact 'same' correlation value at lag j by one 256-thread workgroup (valid in thread 0), float64:
+// same[j] = sum_t a[t + j + (nb-1)//2 - (nb-1)] b[t] / (|a| |b|).  THE summation order of every value that enters a delay,
+// shared by the single and the batched search.
+__device__ inline double xc_exact_256(const double* __restrict__ a, int64_t na, const double* __restrict__ b, int64_t nb,
+                                      const double* __restrict__ norms, int64_t j, double* part /* LDS [4] */) {
+  double acc = 0.0;
+  if (j >= 0 && j < na) {
+    const int64_t sh = j + (nb - 1) / 2 - (nb - 1);
+    for (int64_t t = threadIdx.x; t < nb; t += 256) {
+      const int64_t ia = t + sh;
+      if (ia >= 0 && ia < na) acc += a[ia] * b[t];
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return threadIdx.x == 0 ? (part[0] + part[1] + part[2] + part[3]) / (norms[0] * norms[1]) : 0.0;
+}
 // exact 'same' correlation value at every listed lag (one workgroup per entry, float64)
 __global__ __launch_bounds__(256) void k_xc_exact_list(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
                                                        int64_t nb, const double* __restrict__ norms,
                                                        const long long* __restrict__ list, double* __restrict__ vals) {
   __shared__ double part[4];
-  const int64_t j = list[blockIdx.x];
-  double acc = 0.0;
-  if (j >= 0 && j < na) {
-    const int64_t sh = j + (nb - 1) / 2 - (nb - 1);
-    for (int64_t t = threadIdx.x; t < nb; t += 256) {
-      const int64_t ia = t + sh;
-      if (ia >= 0 && ia < na) acc += a[ia] * b[t];
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) vals[blockIdx.x] = (part[0] + part[1] + part[2] + part[3]) / (norms[0] * norms[1]);
+  const double v = xc_exact_256(a, na, b, nb, norms, list[blockIdx.x], part);
+  if (threadIdx.x == 0) vals[blockIdx.x] = v;
 }
-// exact 'same' correlation values at lags c0 .. c0+count-1 (one workgroup per lag, float64):
-// same[j] = sum_t a[t + j + (nb-1)//2 - (nb-1)] b[t] / (|a| |b|)
+// exact 'same' correlation values at lags c0 .. c0+count-1 (one workgroup per lag, float64)
 __global__ __launch_bounds__(256) void k_xc_exact(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
                                                   int64_t nb, const double* __restrict__ norms, const long long* __restrict__ arg,
                                                   int64_t rel0, double* __restrict__ vals) {
   __shared__ double part[4];
-  const int64_t j = *arg + rel0 + blockIdx.x;
-  double acc = 0.0;
-  if (j >= 0 && j < na) {
-    const int64_t sh = j + (nb - 1) / 2 - (nb - 1);
-    for (int64_t t = threadIdx.x; t < nb; t += 256) {
-      const int64_t ia = t + sh;
-      if (ia >= 0 && ia < na) acc += a[ia] * b[t];
+  const double v = xc_exact_256(a, na, b, nb, norms, *arg + rel0 + blockIdx.x, part);
+  if (threadIdx.x == 0) vals[blockIdx.x] = v;
+}
+
+// ---- X2 batch: find_delay for n_win pairs of rows of one shape (pytapesynch_gui.py:210-238, the azimuth mode) ----------
+// The work per window is par_find_delay_f64's, decided on the device: no value travels to the host between the stages.
+// Per window w the tables in scratch are XcbRow (norms, the transform's top, the rival list and its exact values, the
+// seven exact values around the peak and the f[-1] wrap).
+struct XcbRow {
+  double norms[2];
+  long long arg;
+  int n_cand, pad;
+  long long cand[kXcCand + 1];
+  double cvals[kXcCand + 1];
+  double vals[8];                                  // lags arg-3 .. arg+3, and lag na-1 (numpy's f[-1] at peak 0)
+};
+// rows *= window, in place like util/correlation.py:18-20 (grid: x over samples, y over windows)
+__global__ __launch_bounds__(256) void k_xcb_window(double* __restrict__ a, int64_t a_pitch, int64_t na, double* __restrict__ b,
+                                                    int64_t b_pitch, int64_t nb, const double* __restrict__ win_a,
+                                                    const double* __restrict__ win_b) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, w = blockIdx.y;
+  if (win_a && i < na) a[w * a_pitch + i] *= win_a[i];
+  if (win_b && i < nb) b[w * b_pitch + i] *= win_b[i];
+}
+__global__ __launch_bounds__(1024) void k_xcb_norms(const double* __restrict__ a, int64_t a_pitch, int64_t na,
+                                                    const double* __restrict__ b, int64_t b_pitch, int64_t nb,
+                                                    XcbRow* __restrict__ rows) {
+  __shared__ double part[16];
+  const int64_t w = blockIdx.y;
+  const double t = xc_norm_1024(blockIdx.x ? b + w * b_pitch : a + w * a_pitch, blockIdx.x ? nb : na, part);
+  if (threadIdx.x == 0) rows[w].norms[blockIdx.x] = t;
+}
+__global__ __launch_bounds__(256) void k_xcb_pack(const double* __restrict__ a, int64_t a_pitch, int64_t na,
+                                                  const double* __restrict__ b, int64_t b_pitch, int64_t nb,
+                                                  const XcbRow* __restrict__ rows, float2* __restrict__ Z, int64_t N) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, w = blockIdx.y;
+  if (i >= N) return;
+  const double* ar = a + w * a_pitch;
+  const double* br = b + w * b_pitch;
+  Z[w * N + i] = make_float2(i < na ? (float)(ar[i] / rows[w].norms[0]) : 0.0f, i < nb ? (float)(br[i] / rows[w].norms[1]) : 0.0f);
+}
+__global__ __launch_bounds__(256) void k_xcb_cross(const float2* __restrict__ Z, float2* __restrict__ C, int64_t N) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x, w = blockIdx.y;
+  if (k >= N) return;
+  const float2 zk = Z[w * N + k], zc = cconj(Z[w * N + ((N - k) & (N - 1))]);
+  const float2 A = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
+  const float2 d = csub(zk, zc);
+  const float2 B = make_float2(0.5f * d.y, -0.5f * d.x);
+  const float2 c = cmul(A, cconj(B));
+  C[w * N + k] = cconj(c);
+}
+// One workgroup per window: the 'same' span is read straight out of the second transform's output -- the float64 'full'
+// array of the single call, full[j] = (double)Y[(j - (nb-1)) mod N].x / N, is formed value by value and never stored --
+// first argmax (k_xc_argmax's order), then the rival list (k_xc_candidates' rule) in LDS.
+__global__ __launch_bounds__(256) void k_xcb_peak(const float2* __restrict__ Y, int64_t N, int64_t na, int64_t nb, int use_abs,
+                                                  double tol, XcbRow* __restrict__ rows) {
+  __shared__ double bv[256];
+  __shared__ long long bi[256];
+  __shared__ long long lcand[kXcCand];
+  __shared__ int lcount;
+  const int64_t w = blockIdx.x;
+  const float2* Yw = Y + w * N;
+  const int64_t off = (nb - 1) / 2 - (nb - 1);
+  const double dN = (double)N;
+  auto same = [&](int64_t j) {
+    const double x = (double)Yw[(j + off) & (N - 1)].x / dN;
+    return use_abs ? fabs(x) : x;
+  };
+  double best = -INFINITY;
+  long long at = 0;
+  for (int64_t i = threadIdx.x; i < na; i += 256) {
+    const double x = same(i);
+    if (x > best) {
+      best = x;
+      at = i;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  bv[threadIdx.x] = best;
+  bi[threadIdx.x] = at;
+  if (threadIdx.x == 0) lcount = 0;
   __syncthreads();
-  if (threadIdx.x == 0) vals[blockIdx.x] = (part[0] + part[1] + part[2] + part[3]) / (norms[0] * norms[1]);
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      const double x = bv[threadIdx.x + o];
+      const long long j = bi[threadIdx.x + o];
+      if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && j < bi[threadIdx.x])) {
+        bv[threadIdx.x] = x;
+        bi[threadIdx.x] = j;
+      }
+    }
+    __syncthreads();
+  }
+  const long long top = bi[0];
+  const double m = same(top);
+  for (int64_t i = threadIdx.x; i < na; i += 256) {
+    if (i >= top - 2 && i <= top + 2) continue;
+    const double x = same(i);
+    if (!(x >= m - tol)) continue;
+    const double xl = i > 0 ? same(i - 1) : -INFINITY;
+    const double xr = i + 1 < na ? same(i + 1) : -INFINITY;
+    if (x >= xl && x >= xr) {
+      const int slot = atomicAdd(&lcount, 1);
+      if (slot < kXcCand) lcand[slot] = i;
+    }
+  }
+  __syncthreads();
+  const int nc = lcount;
+  XcbRow& r = rows[w];
+  if (nc > 0 && nc < kXcCand) {                    // as many rivals as slots or more: a plateau, the transform's top stands
+    if (threadIdx.x < nc) r.cand[threadIdx.x] = lcand[threadIdx.x];
+    if (threadIdx.x == 0) r.cand[nc] = top;       // the top goes into slot nc
+  }
+  if (threadIdx.x == 0) {
+    r.arg = top;
+    r.n_cand = nc;
+  }
+}
+// exact values of the listed rivals and the top: grid (kXcCand, windows), entries behind the list return at once
+__global__ __launch_bounds__(256) void k_xcb_exact_list(const double* __restrict__ a, int64_t a_pitch, int64_t na,
+                                                        const double* __restrict__ b, int64_t b_pitch, int64_t nb,
+                                                        XcbRow* __restrict__ rows) {
+  __shared__ double part[4];
+  const int64_t w = blockIdx.y;
+  XcbRow& r = rows[w];
+  const int nc = r.n_cand;
+  if (!(nc > 0 && nc < kXcCand) || (int)blockIdx.x > nc) return;
+  const double v = xc_exact_256(a + w * a_pitch, na, b + w * b_pitch, nb, r.norms, r.cand[blockIdx.x], part);
+  if (threadIdx.x == 0) r.cvals[blockIdx.x] = v;
+}
+// the exact values decide, the lowest lag wins a tie (np.argmax returns the first maximum): one thread per window
+__global__ __launch_bounds__(64) void k_xcb_decide(XcbRow* __restrict__ rows, int64_t count, int use_abs) {
+  const int64_t w = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (w >= count) return;
+  XcbRow& r = rows[w];
+  const int nc = r.n_cand;
+  if (!(nc > 0 && nc < kXcCand)) return;
+  int best = nc;
+  for (int c = 0; c < nc; ++c) {
+    const double x = use_abs ? fabs(r.cvals[c]) : r.cvals[c], y = use_abs ? fabs(r.cvals[best]) : r.cvals[best];
+    if (x > y || (x == y && r.cand[c] < r.cand[best])) best = c;
+  }
+  r.arg = r.cand[best];
+}
+// exact values at arg-3 .. arg+3 (blockIdx.x 0 .. 6) and, where the final peak can be lag 0 (arg <= 2), at lag na-1
+__global__ __launch_bounds__(256) void k_xcb_exact7(const double* __restrict__ a, int64_t a_pitch, int64_t na,
+                                                    const double* __restrict__ b, int64_t b_pitch, int64_t nb,
+                                                    XcbRow* __restrict__ rows) {
+  __shared__ double part[4];
+  const int64_t w = blockIdx.y;
+  XcbRow& r = rows[w];
+  const long long p0 = r.arg;
+  if (blockIdx.x == 7 && p0 > 2) return;
+  const int64_t j = blockIdx.x == 7 ? na - 1 : p0 - 3 + (int64_t)blockIdx.x;
+  const double v = xc_exact_256(a + w * a_pitch, na, b + w * b_pitch, nb, r.norms, j, part);
+  if (threadIdx.x == 0) r.vals[blockIdx.x] = v;
+}
+// best of arg-2 .. arg+2, the status and parabolic() (util/correlation.py:42-46), one thread per window.  The arithmetic is
+// par_find_delay_f64's host arithmetic, rounding by rounding: no contraction into FMAs here.
+__global__ __launch_bounds__(64) void k_xcb_final(const XcbRow* __restrict__ rows, int64_t count, int64_t na, int use_abs,
+                                                  double* __restrict__ delay, double* __restrict__ corr, int32_t* __restrict__ status) {
+#pragma clang fp contract(off)
+  const int64_t w = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (w >= count) return;
+  const XcbRow& r = rows[w];
+  const long long p0 = r.arg;
+  const double* v = r.vals;
+  int best = 3;
+  for (int c = 1; c <= 5; ++c) {
+    const long long j = p0 - 3 + c;
+    if (j < 0 || j >= na) continue;
+    const double x = use_abs ? fabs(v[c]) : v[c], y = use_abs ? fabs(v[best]) : v[best];
+    if (x > y || (x == y && c < best)) best = c;
+  }
+  const long long peak = p0 - 3 + best;
+  if (peak == na - 1) {                              // the reference's IndexError in parabolic(), for this row only
+    delay[w] = NAN;
+    corr[w] = NAN;
+    status[w] = 1;
+    return;
+  }
+  const double fm = peak == 0 ? v[7] : v[best - 1], f0 = v[best], fp = v[best + 1];
+  const double xv = 0.5 * (fm - fp) / (fm - 2.0 * f0 + fp) + (double)peak;
+  corr[w] = f0 - 0.25 * (fm - fp) * (xv - (double)peak);
+  delay[w] = xv - (double)(na / 2);
+  status[w] = 0;
+}
+
+// out[w][i] = (double)sig[(starts[w] + i - pad_l[w]) * stride] inside the window's samples, 0.0 in its padding
+// (Spectrum.get_signal, util/spectrum.py:158-171, for a batch of windows; grid: x over samples, y over windows)
+__global__ __launch_bounds__(256) void k_gather_windows(const float* __restrict__ sig, int64_t sig_stride, int64_t n,
+                                                        const long long* __restrict__ starts, const long long* __restrict__ lens,
+                                                        const long long* __restrict__ pad_l, int64_t w0, int64_t n_out,
+                                                        double* __restrict__ out, int64_t out_pitch) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, w = w0 + blockIdx.y;
+  if (i >= n_out) return;
+  const long long k = i - pad_l[w], src = starts[w] + k;
+  double v = 0.0;
+  if (k >= 0 && k < lens[w] && src >= 0 && src < n) v = (double)sig[src * sig_stride];
+  out[w * out_pitch + i] = v;
 }
 
 // ISTFT stage 1: frame f -> window * irfft(spec[f] * sqrt(n_fft))   (util/fourier.py:359, :401)
@@ -1888,6 +2084,104 @@ int par_find_delay_f64(int device, const double* a, int64_t na, const double* b,
   const double xv = 0.5 * (fm - fp) / (fm - 2.0 * f0 + fp) + (double)peak;
   *corr = f0 - 0.25 * (fm - fp) * (xv - (double)peak);
   *delay = xv - (double)(na / 2);
+  return PAR_OK;
+}
+
+// X2 batch: find_delay for n_win pairs of rows (a[w * a_pitch ..], b[w * b_pitch ..]) of one shape (na, nb), every window
+// decided on the device (the kernels above).  Windows are processed in passes of as many as scratch_bytes holds: per window
+// two N-point complex arrays and one XcbRow.  Nothing synchronises here but big_fft_c2c's table upload on a device's
+// first call of a size.
+constexpr size_t kXcbCap = (size_t)1 << 30;        // transform arrays of one pass
+constexpr int64_t kXcbMaxPass = 32768;             // windows of one pass (the y extent of a grid)
+static size_t xcb_window_bytes(int64_t N) { return (size_t)(2 * N) * sizeof(float2) + sizeof(par::XcbRow); }
+size_t par_find_delay_batch_scratch_bytes(int64_t na, int64_t nb, int64_t n_win) {
+  if (na < 1 || nb < 1 || na + nb - 1 > kXcMaxFft) return 0;
+  const int64_t N = xc_fft_len(na, nb);
+  int64_t fit = (int64_t)(kXcbCap / ((size_t)(2 * N) * sizeof(float2)));
+  if (fit > kXcbMaxPass) fit = kXcbMaxPass;
+  int64_t c = n_win < 1 ? 1 : n_win;
+  if (c > fit) c = fit;
+  return (size_t)c * xcb_window_bytes(N);
+}
+int par_find_delay_batch_f64(int device, double* a, int64_t a_pitch, int64_t na, double* b, int64_t b_pitch, int64_t nb,
+                             int64_t n_win, const double* win_a, const double* win_b, int ignore_phase, void* scratch,
+                             size_t scratch_bytes, double* delay, double* corr, int32_t* status, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(a && b && scratch && delay && corr && status, PAR_ERR_ARG, "par_find_delay_batch_f64: null pointer");
+  PAR_REQUIRE(na >= 3 && nb >= 1 && n_win >= 0, PAR_ERR_ARG, "par_find_delay_batch_f64: na %lld (>= 3), nb %lld (>= 1), n_win %lld (>= 0)",
+              (long long)na, (long long)nb, (long long)n_win);
+  PAR_REQUIRE(a_pitch >= na && b_pitch >= nb, PAR_ERR_ARG, "par_find_delay_batch_f64: pitch %lld / %lld below the row length %lld / %lld",
+              (long long)a_pitch, (long long)b_pitch, (long long)na, (long long)nb);
+  if (n_win == 0) return PAR_OK;
+  PAR_REQUIRE(na + nb - 1 <= kXcMaxFft, PAR_ERR_UNSUPPORTED,
+              "par_find_delay_batch_f64: %lld + %lld - 1 lags need the sectioned form, which is not batched (limit 2^20)", (long long)na,
+              (long long)nb);
+  const int64_t N = xc_fft_len(na, nb);
+  int64_t C = (int64_t)(scratch_bytes / xcb_window_bytes(N));
+  PAR_REQUIRE(C >= 1, PAR_ERR_WORKSPACE, "par_find_delay_batch_f64: scratch holds less than one window (%zu bytes)", xcb_window_bytes(N));
+  if (C > kXcbMaxPass) C = kXcbMaxPass;
+  if (C > n_win) C = n_win;
+  PAR_HIP_CHECK(hipSetDevice(device));
+  hipStream_t s = as_stream(stream);
+  float2* Z = static_cast<float2*>(scratch);
+  float2* Y = Z + C * N;
+  XcbRow* rows = reinterpret_cast<XcbRow*>(Y + C * N);
+  const int64_t nmax = na > nb ? na : nb;
+  for (int64_t w0 = 0; w0 < n_win; w0 += C) {
+    const int64_t c = n_win - w0 < C ? n_win - w0 : C;
+    double* ac = a + w0 * a_pitch;
+    double* bc = b + w0 * b_pitch;
+    const dim3 gN((unsigned)ceil_div(N, 256), (unsigned)c);
+    if (win_a || win_b)
+      hipLaunchKernelGGL(k_xcb_window, dim3((unsigned)ceil_div(nmax, 256), (unsigned)c), dim3(256), 0, s, ac, a_pitch, na, bc, b_pitch, nb,
+                         win_a, win_b);
+    hipLaunchKernelGGL(k_xcb_norms, dim3(2, (unsigned)c), dim3(1024), 0, s, (const double*)ac, a_pitch, na, (const double*)bc, b_pitch,
+                       nb, rows);
+    hipLaunchKernelGGL(k_xcb_pack, gN, dim3(256), 0, s, (const double*)ac, a_pitch, na, (const double*)bc, b_pitch, nb,
+                       (const XcbRow*)rows, Z, N);
+    int rc = big_fft_c2c(device, Z, Y, N, c, s);                        // Y = FFT(a + i b), window by window
+    if (rc != PAR_OK) return rc;
+    hipLaunchKernelGGL(k_xcb_cross, gN, dim3(256), 0, s, (const float2*)Y, Z, N);
+    rc = big_fft_c2c(device, Z, Y, N, c, s);                            // Y = conj(N * circular correlation)
+    if (rc != PAR_OK) return rc;
+    hipLaunchKernelGGL(k_xcb_peak, dim3((unsigned)c), dim3(256), 0, s, (const float2*)Y, N, na, nb, ignore_phase, kXcRivalTol, rows);
+    hipLaunchKernelGGL(k_xcb_exact_list, dim3(kXcCand, (unsigned)c), dim3(256), 0, s, (const double*)ac, a_pitch, na, (const double*)bc,
+                       b_pitch, nb, rows);
+    hipLaunchKernelGGL(k_xcb_decide, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, s, rows, c, ignore_phase);
+    hipLaunchKernelGGL(k_xcb_exact7, dim3(8, (unsigned)c), dim3(256), 0, s, (const double*)ac, a_pitch, na, (const double*)bc, b_pitch,
+                       nb, rows);
+    hipLaunchKernelGGL(k_xcb_final, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, s, (const XcbRow*)rows, c, na, ignore_phase,
+                       delay + w0, corr + w0, status + w0);
+    PAR_HIP_CHECK(hipGetLastError());
+  }
+  return PAR_OK;
+}
+
+// Spectrum.get_signal (util/spectrum.py:158-171) for n_win windows of one channel: see include/par_hip.h.  The geometry is
+// checked on the host, from the caller's host copy, before anything is launched.
+int par_gather_windows_f64(int device, const float* sig, int64_t sig_stride, int64_t n, const int64_t* starts, const int64_t* lens,
+                           const int64_t* pad_l, const int64_t* host_geom, int64_t n_win, int64_t n_out, double* out,
+                           int64_t out_pitch, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(sig && starts && lens && pad_l && host_geom && out, PAR_ERR_ARG, "par_gather_windows_f64: null pointer");
+  PAR_REQUIRE(sig_stride >= 1 && n >= 0 && n_win >= 0 && n_out >= 0 && out_pitch >= n_out, PAR_ERR_ARG,
+              "par_gather_windows_f64: stride %lld, n %lld, n_win %lld, n_out %lld, pitch %lld", (long long)sig_stride, (long long)n,
+              (long long)n_win, (long long)n_out, (long long)out_pitch);
+  for (int64_t w = 0; w < n_win; ++w) {
+    const int64_t st = host_geom[w], ln = host_geom[n_win + w], pl = host_geom[2 * n_win + w];
+    PAR_REQUIRE(st >= 0 && ln >= 0 && pl >= 0 && st <= n && ln <= n - st && pl <= n_out && ln <= n_out - pl, PAR_ERR_ARG,
+                "par_gather_windows_f64: window %lld (start %lld, length %lld, pad %lld) leaves the %lld-sample signal or the %lld-sample row",
+                (long long)w, (long long)st, (long long)ln, (long long)pl, (long long)n, (long long)n_out);
+  }
+  if (n_win == 0 || n_out == 0) return PAR_OK;
+  PAR_HIP_CHECK(hipSetDevice(device));
+  for (int64_t w0 = 0; w0 < n_win; w0 += kXcbMaxPass) {
+    const int64_t c = n_win - w0 < kXcbMaxPass ? n_win - w0 : kXcbMaxPass;
+    hipLaunchKernelGGL(k_gather_windows, dim3((unsigned)ceil_div(n_out, 256), (unsigned)c), dim3(256), 0, as_stream(stream), sig,
+                       sig_stride, n, reinterpret_cast<const long long*>(starts), reinterpret_cast<const long long*>(lens),
+                       reinterpret_cast<const long long*>(pad_l), w0, n_out, out, out_pitch);
+  }
+  PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }
 

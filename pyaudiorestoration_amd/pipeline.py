@@ -8,6 +8,8 @@ util/spectrum.py:384-385 (spectra are computed with 'blackmanharris').
 Here: STFT magnitude (K_stft) -> tracker (K_track) -> master speed curve (K_sosfiltfilt) ->
 positions (K_pos) -> sinc resample (K_sinc), with the signal and spectrogram resident in HBM.
 """
+import collections
+import ctypes
 import warnings
 
 import logging
@@ -502,15 +504,22 @@ def heal_heuristic(signal, sr, fft_size=512, hop=64, max_width=0.02, max_slope=0
 
 
 # ---------------------------------------------------------------------- tape synchronisation (pytapesynch)
-def lag_curve_from_markers(markers, duration, sr, hop, smoothing=3, bands=(0, 9999999)):
+def lag_curve_from_markers(markers, duration, sr, hop, smoothing=3, bands=(0, 9999999), azimuths=()):
     """Lag curve (N, 2) = (time s, lag s) from tape-sync markers -- headless restatement of LagLine
-    (util/markers.py:730-790) for projects without azimuth lines: markers are LagSample.to_cfg() tuples
+    (util/markers.py:730-790): markers are LagSample.to_cfg() tuples
     (a_t, a_f, b_t, b_f, d, corr) (util/markers.py:478-479), a marker sits at t = (a_t + b_t)/2 with lag d.
     The lag is an interpolating spline of order min(smoothing, n-1) through the markers (:737-747), sampled at
     marker rate sr/hop on [0, |duration + lag(duration)|] (:749-758) and band-limited like every BaseLine
     (:601-605; the default band lets everything through).  This is what pytapesynch hands to
-    resampling.run(lag_curve=...) (pytapesynch_gui.py:145-155)."""
+    resampling.run(lag_curve=...) (pytapesynch_gui.py:145-155).
+    azimuths: azimuth lines, each (times, lags, corrs, lower, upper) as AzimuthLine.to_cfg() writes them, or an AzimuthLine of
+    azimuth_line().  With lines, LagLine.sample_at (:760-777) and BaseLine.sample_lines (:607-615) are restated: every line
+    is np.interp'd with NaN outside its span into a FLOAT32 array, np.nanmean runs across the lines, and the samples no line
+    covers take the markers' spline (zeros without markers) -- rounded to float32 too, as the reference assigns them into
+    that array.  Without lines the function's results are what they were before the keyword existed."""
     from scipy.interpolate import InterpolatedUnivariateSpline
+    if len(azimuths):
+        return _lag_curve_with_azimuths(markers, duration, sr, hop, smoothing, bands, azimuths)
     pts = sorted(((m[0] + m[2]) / 2, m[4]) for m in markers)
     keys = np.array([p[0] for p in pts], dtype=np.float64)
     lags = np.array([p[1] for p in pts], dtype=np.float64)
@@ -549,18 +558,234 @@ def correlate_sources(ref_sig, src_sig, sr, lower, upper, ignore_phase=False, wi
     return sample_delay / sr * speed, corr
 
 
+def _lag_curve_with_azimuths(markers, duration, sr, hop, smoothing, bands, azimuths):
+    """LagLine.get_times / sample_at / update (util/markers.py:749-790) with azimuth lines (lag_curve_from_markers)."""
+    from scipy.interpolate import InterpolatedUnivariateSpline
+    pts = sorted(((m[0] + m[2]) / 2, m[4]) for m in markers)
+    keys = np.array([p[0] for p in pts], dtype=np.float64)
+    lags = np.array([p[1] for p in pts], dtype=np.float64)
+    lines = [(np.asarray(az[0], dtype=np.float64), np.asarray(az[1], dtype=np.float64)) for az in azimuths]
+
+    def sample_at(times):
+        if len(keys) == 0:
+            spline = np.interp(times, (0,), (0,))
+        elif len(keys) == 1:
+            spline = np.interp(times, keys, lags)
+        else:
+            spline = InterpolatedUnivariateSpline(keys, lags, k=min(smoothing, len(keys) - 1))(times)
+        out = np.zeros((len(times), len(lines)), dtype=np.float32)                 # BaseLine.sample_lines (:607-615)
+        for i, (line_times, line_values) in enumerate(lines):
+            out[:, i] = np.interp(times, line_times, line_values, left=np.nan, right=np.nan)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=RuntimeWarning)
+            sampled = np.nanmean(out, axis=1)
+        nans = np.isnan(sampled)
+        sampled[nans] = spline[nans]                                               # (:774-775) into the float32 array
+        return sampled
+
+    dur = duration                                                                 # LagLine.get_times (:749-758), type by type
+    dur += sample_at((dur,))[0]
+    dur = abs(dur)
+    marker_sr = sr / hop
+    times = np.linspace(0, dur, num=int(dur * marker_sr))
+    lo, hi = sorted(bands)
+    return np.stack((times, filters.butter_bandpass_filter(sample_at(times), lo, hi, marker_sr, order=3)), axis=-1)
+
+
+def times_freqs(a, b, sr):
+    """Spectrum.get_times_freqs (util/spectrum.py:173-178): two corners (t, f) of a selection -> (t0, t1, lower, upper)
+    with the band clamped to [1, sr // 2 - 1]."""
+    t0, t1 = sorted((a[0], b[0]))
+    freqs = sorted((a[1], b[1]))
+    return t0, t1, max(freqs[0], 1), min(freqs[1], sr // 2 - 1)
+
+
+def _get_signal_geometry(t0, t1, sr, length):
+    """(start, length, pad_l, pad_r) of Spectrum.get_signal(t0, t1) (util/spectrum.py:158-171) on a signal of `length`
+    samples: int() truncates toward zero, the left pad is |sample0| when it is negative, the slice signal[sample0:sample1]
+    keeps Python's meaning of a negative start (it counts from the END of the file), the right pad is sample1 - length."""
+    sample0, sample1 = int(t0 * sr), int(t1 * sr)
+    pad_l = abs(sample0) if sample0 < 0 else 0
+    pad_r = sample1 - length if sample1 > length else 0
+    start, stop, _ = slice(sample0, sample1).indices(length)
+    return start, max(0, stop - start), pad_l, pad_r
+
+
+def azimuth_windows(len_ref, len_src, sr, t0, t1, lag_curve, dur, overlap):
+    """The windows of the tape-sync tool's azimuth mode (pytapesynch_gui.py:210-238), host integer logic only:
+    -> (sample_times, sample_lags, ref_geom, src_geom); sample_times = np.arange(t0, t1, dur / overlap), sample_lags the
+    lag curve (rows (t, lag)) interpolated there, *_geom int64 (W, 4) rows (start, length, pad_l, pad_r) of the two
+    Spectrum.get_signal calls Canvas.correlate_sources (:108-125) makes for window x with lag d: the reference file
+    around x, the source file around x - d, both of half width dur.  The times go through correlate_sources' own
+    arithmetic (t_center = (t0 + t1) / 2, t_width = (t1 - t0) / 2, get_signal_around's t -+ width), so a sample index
+    that sits on a rounding edge falls where the reference's falls.  An empty np.arange gives empty results."""
+    sample_times = np.arange(t0, t1, dur / overlap)
+    lag_curve = np.asarray(lag_curve, dtype=np.float64)
+    sample_lags = np.interp(sample_times, lag_curve[:, 0], lag_curve[:, 1]) if len(sample_times) else np.zeros(0)
+    ref_geom = np.zeros((len(sample_times), 4), dtype=np.int64)
+    src_geom = np.zeros((len(sample_times), 4), dtype=np.int64)
+    for i, (x, d) in enumerate(zip(sample_times, sample_lags)):
+        w0, w1 = x - dur, x + dur
+        t_center, t_width = (w0 + w1) / 2, (w1 - w0) / 2
+        ref_geom[i] = _get_signal_geometry(t_center - t_width, t_center + t_width, sr, len_ref)
+        c = t_center - d
+        src_geom[i] = _get_signal_geometry(c - t_width, c + t_width, sr, len_src)
+    return sample_times, sample_lags, ref_geom, src_geom
+
+
+def azimuth_reject(lags_raw, corrs, overlap, reject):
+    """AzimuthLine.update_reject (util/markers.py:542-552): the raw lags, NaN where |corr| < reject, the NaNs interpolated
+    over (wow_detection.interp_nans), then a median filter of make_odd(overlap) samples with 'nearest' edges.  O(W) host
+    work.  A line without one accepted sample stays all NaN (the reference's np.interp raises on it)."""
+    import scipy.ndimage
+    lags = np.array(lags_raw, dtype=np.float64)
+    lags[np.abs(np.asarray(corrs)) < reject] = np.nan
+    if len(lags) == 0 or np.all(np.isnan(lags)):
+        return lags
+    wow_detection.interp_nans(lags)
+    return scipy.ndimage.median_filter(lags, size=filters.make_odd(overlap), mode='nearest')
+
+
+class AzimuthLine(collections.namedtuple("AzimuthLine", "times lags corrs lower upper lags_raw")):
+    """One azimuth line (util/markers.py:483-563): lags = azimuth_reject(lags_raw, ...)."""
+    __slots__ = ()
+
+    def to_cfg(self):
+        """AzimuthLine.to_cfg (:562-563): what a .tapesync project stores under "azimuths"."""
+        return [float(v) for v in self.times], [float(v) for v in self.lags], [float(v) for v in self.corrs], \
+            float(self.lower), float(self.upper)
+
+
+def _channel_dev(sig, channel, dev):
+    """(flat float32 device view of the file, stride, samples, offset of the channel)"""
+    sig_t = _dev.to_dev(sig if torch.is_tensor(sig) else np.ascontiguousarray(sig), torch.float32, dev)
+    if sig_t.ndim == 1:
+        if channel != 0:
+            raise ValueError(f"channel {channel} of a mono signal")
+        return sig_t, 1, sig_t.shape[0], 0
+    n, ch = sig_t.shape
+    if not 0 <= channel < ch:
+        raise ValueError(f"channel {channel} of {ch}")
+    return sig_t.reshape(-1), ch, n, channel
+
+
+def gather_windows_dev(flat_t, stride, n, channel, geom, n_out, dev):
+    """par_gather_windows_f64: the windows `geom` (rows (start, length, pad_l, pad_r)) of one channel of an interleaved
+    float32 device file as float64 rows (W, n_out), zero in the padding."""
+    from . import _lib
+    W = len(geom)
+    host = np.ascontiguousarray(geom[:, :3].T, dtype=np.int64)                     # [3][W]: starts, lens, pad_l
+    geo_t = _dev.to_dev(host, torch.int64, dev)
+    out = _dev.empty((W, n_out), torch.float64, dev)
+    _lib.check(_lib.lib().par_gather_windows_f64(dev, _dev.ptr(flat_t[channel:]), stride, n, _dev.ptr(geo_t[0]), _dev.ptr(geo_t[1]),
+                                                 _dev.ptr(geo_t[2]), host.ctypes.data_as(ctypes.c_void_p), W, n_out, _dev.ptr(out),
+                                                 n_out, _dev.stream_ptr(dev)))
+    return out
+
+
+_AZIMUTH_MAX_ROWS = 32768          # rows of one chunk: par_sosfiltfilt_batch_f64 takes 65 535 per call, one pass of the search 32 768
+
+
+def azimuth_line(ref_sig, src_sig, sr, t0, t1, lower, upper, lag_curve, dur=0.2, overlap=32, reject=0.1, ignore_phase=False,
+                 ref_channel=0, src_channel=0, max_bytes=1 << 30):
+    """The tape-sync tool's azimuth mode (Canvas.on_mouse_release, `Alt` branch, pytapesynch_gui.py:210-238; match_speed
+    off) for the selection [t0, t1) x [lower, upper] (already clamped: times_freqs): every dur / overlap seconds a window
+    of 2 dur seconds is cut out of both files (the source file at the lag the current lag curve gives), both are
+    band-passed (order-3 zero-phase Butterworth), Hann-windowed and correlated, and the refined delay is added to the lag.
+    Both files go to the device once as float32; the windows are grouped by their lengths (na, nb) and every group runs, in
+    chunks of at most max_bytes of device memory, through par_gather_windows_f64, K_sosfiltfilt's batched form and
+    par_find_delay_batch_f64 -- five library calls per chunk where the loop over correlate_sources makes three per window.  A
+    group whose shape the batch refuses runs through correlate_sources window by window.  -> AzimuthLine.  A window whose
+    peak sits on the last lag raises the reference's IndexError."""
+    from . import _lib, correlation
+    dev = _dev.device_index(None)
+    ref_flat, ref_stride, len_ref, ref_c = _channel_dev(ref_sig, ref_channel, dev)
+    src_flat, src_stride, len_src, src_c = _channel_dev(src_sig, src_channel, dev)
+    times, sample_lags, ref_geom, src_geom = azimuth_windows(len_ref, len_src, sr, t0, t1, lag_curve, dur, overlap)
+    W = len(times)
+    time_delays, corrs = np.zeros(W), np.zeros(W)                       # seconds, as correlate_sources returns them
+    na_all = ref_geom[:, 1] + ref_geom[:, 2] + ref_geom[:, 3]
+    nb_all = src_geom[:, 1] + src_geom[:, 2] + src_geom[:, 3]
+    groups = {}
+    for i in range(W):
+        groups.setdefault((int(na_all[i]), int(nb_all[i])), []).append(i)
+    for (na, nb), idx in groups.items():
+        idx = np.asarray(idx)
+        try:
+            per_window = correlation.batch_scratch_bytes(na, nb, 1) + 5 * 8 * (na + nb)    # + gathered rows, filter output and work
+            batched = True
+        except _lib.ParUnsupported:
+            per_window, batched = 5 * 8 * (na + nb), False
+        chunk = int(max(1, min(len(idx), max_bytes // per_window, _AZIMUTH_MAX_ROWS)))
+        for c0 in range(0, len(idx), chunk):
+            sel = idx[c0:c0 + chunk]
+            a_t = gather_windows_dev(ref_flat, ref_stride, len_ref, ref_c, ref_geom[sel], na, dev)
+            b_t = gather_windows_dev(src_flat, src_stride, len_src, src_c, src_geom[sel], nb, dev)
+            if batched:
+                a_f = filters.bandpass_batch_dev(a_t, lower, upper, sr, order=3, dev=dev)
+                b_f = filters.bandpass_batch_dev(b_t, lower, upper, sr, order=3, dev=dev)
+                d_t, c_t, s_t = correlation.find_delay_batch_dev(a_f, b_f, ignore_phase, "hann", dev)
+                status = s_t.cpu().numpy()
+                if np.any(status == 1):
+                    k = int(sel[int(np.flatnonzero(status == 1)[0])])
+                    raise IndexError(f"index {na} is out of bounds for axis 0 with size {na} (azimuth window {k} at {times[k]} s)")
+                time_delays[sel], corrs[sel] = _dev.to_host(d_t) / sr, _dev.to_host(c_t)
+            else:
+                for k, a_row, b_row in zip(sel, a_t, b_t):
+                    time_delays[k], corrs[k] = correlate_sources(a_row, b_row, sr, lower, upper, ignore_phase, "hann")
+    lags_raw = sample_lags + time_delays
+    return AzimuthLine(times, azimuth_reject(lags_raw, corrs, overlap, reject), corrs, lower, upper, lags_raw)
+
+
+def project_lag_curve(cfg, duration, sr):
+    """The lag curve of a saved pytapesynch project: its "markers", or the "lags" and "azimuths" ParamWidget.save writes for
+    STORE = {"lags", "azimuths"} (pytapesynch_gui.py:23, util/widgets.py:1224-1233).  A "markers"-only project takes the
+    path it always took."""
+    hop = cfg["fft_size"] // cfg.get("fft_overlap", 1)
+    if "lags" not in cfg and "azimuths" not in cfg:
+        return lag_curve_from_markers(cfg["markers"], duration, sr, hop, cfg.get("smoothing", 3))
+    return lag_curve_from_markers(list(cfg.get("markers", ())) + list(cfg.get("lags", ())), duration, sr, hop, cfg.get("smoothing", 3),
+                                  azimuths=tuple(cfg.get("azimuths", ())))
+
+
+def measure_azimuth(project, ref, src=None, box=None, dur=0.2, overlap=32, reject=0.1, ignore_phase=False, out=None):
+    """`cli azimuth`: measure one azimuth line of a pytapesynch project headless.  ref / src: the two files (src default: the
+    project's "source"); box (t0, f0, t1, f1): the selection in the reference file's spectrogram.  The line is measured
+    against the project's current lag curve, logged, and -- with `out` -- the project is written there with the line
+    appended under "azimuths".  -> (AzimuthLine, project dict)."""
+    import json
+    from . import io_ops
+    cfg = json.load(open(project)) if isinstance(project, (str, bytes)) or hasattr(project, "__fspath__") else dict(project)
+    ref_sig, sr, _ = io_ops.read_file(ref)
+    src_sig, sr_src, _ = io_ops.read_file(src or cfg["source"])
+    if sr_src != sr:
+        raise ValueError(f"sample rates differ: {sr} and {sr_src}")                # (the reference has a todo here, :109)
+    t0, t1, lower, upper = times_freqs((box[0], box[1]), (box[2], box[3]), sr)
+    curve = project_lag_curve(cfg, len(src_sig) / sr, sr) if any(cfg.get(k) for k in ("markers", "lags", "azimuths")) else \
+        np.array([[0.0, 0.0], [999.0, 0.0]])                                       # BaseLine's empty line (:571-573)
+    line = azimuth_line(ref_sig, src_sig, sr, t0, t1, lower, upper, curve, dur, overlap, reject, ignore_phase)
+    logging.info("azimuth line: %d windows, mean lag %.9g s, mean correlation %.6g", len(line.times),
+                 np.mean(line.lags) if len(line.times) else float("nan"), np.mean(line.corrs) if len(line.times) else float("nan"))
+    cfg["azimuths"] = list(cfg.get("azimuths", ())) + [list(line.to_cfg())]
+    if "lags" not in cfg:                                                          # the project now has the GUI's newer layout
+        cfg["lags"] = list(cfg.pop("markers", ()))
+    if out:
+        with open(out, "w") as fh:
+            json.dump(cfg, fh, indent=1)
+    return line, cfg
+
+
 def tapesync(project, source=None, out_suffix=None, device=None):
     """Run a saved pytapesynch project headless: `project` is the path of a .tapesync JSON (util/widgets.py:
-    1224-1233 writes it: fft_size, fft_overlap, markers, source, resampling_mode, sinc_quality, smoothing,
-    suffix) or the dict itself; `source` overrides the audio path stored in it.  Writes <source>_res<suffix>.wav
+    1224-1233 writes it: fft_size, fft_overlap, markers -- or lags and azimuths --, source, resampling_mode, sinc_quality,
+    smoothing, suffix) or the dict itself; `source` overrides the audio path stored in it.  Writes <source>_res<suffix>.wav
     through resampling.run and returns the lag curve."""
     import json
     from . import io_ops
     cfg = json.load(open(project)) if isinstance(project, (str, bytes)) or hasattr(project, "__fspath__") else dict(project)
     path = source or cfg["source"]
     signal, sr, _ = io_ops.read_file(path)
-    hop = cfg["fft_size"] // cfg.get("fft_overlap", 1)
-    curve = lag_curve_from_markers(cfg["markers"], len(signal) / sr, sr, hop, cfg.get("smoothing", 3))
+    curve = project_lag_curve(cfg, len(signal) / sr, sr)
     resampling.run((path,), signal_data=((signal, sr),), lag_curve=curve, resampling_mode=cfg.get("resampling_mode", "Sinc"),
                    sinc_quality=cfg.get("sinc_quality", 50), suffix=cfg.get("suffix", "") if out_suffix is None else out_suffix)
     return curve
