@@ -647,6 +647,52 @@ int par_dynamics_factor_f64(int device, const double* a, const double* b, int64_
  * n_ch, F != ceil(n / hop), out == sig: PAR_ERR_ARG before any device call. */
 int par_dynamics_apply_f32(int device, const float* sig, int64_t sig_stride, int n_ch, int64_t n, const double* fac, int64_t F,
                            int hop, float* out, int64_t out_stride, void* stream);
+/* ---- stereo balance (pypan_gui.py:53-58 run_resample, :78-104 the Shift branch of on_mouse_release) ------------------------------
+ * par_pan_ratio_scratch_bytes, par_pan_ratio_f32, par_stft_pan_scratch_bytes, par_stft_pan_ratio_f32 and par_pan_apply_f32 are
+ * added at ABI 109: par_version() stays 109.  All work on the caller's stream and none synchronises the host.
+ *
+ * A box is four int32 (bin_l, bin_u, frame_0, frame_1), half-open: the integers the reference derives at :81-98 (the host layer's
+ * pypan.box_to_cells).  `boxes` is DEVICE int32[n_box][4], read by the kernels; `boxes_host` is a HOST copy of the same numbers,
+ * from which the call validates every box, sizes its launches and checks the scratch before any device call (as
+ * par_gather_windows_f64 takes its geometry twice).  A box whose bin range leaves [0, bins] or whose frame range leaves
+ * [0, n_frames] is PAR_ERR_ARG (the host layer clamps as the reference does); an empty range inside those limits is legal.
+ * 1 <= n_box <= 65535; at most 2^31 - 1 (box, frame) pairs per call. */
+/* Bytes of DEVICE scratch for these boxes (host only; 0 for a null pointer or n_box outside 1..65535): int64[n_box + 1] offsets,
+ * padded to 16 bytes, and one (float64 sum, int64 count) pair per frame of every box that holds a cell. */
+size_t par_pan_ratio_scratch_bytes(const int32_t* boxes_host, int64_t n_box);
+/* fac[b] (DEVICE f64) = np.nanmean(L[bin_l:bin_u, frame_0:frame_1] / R[...]) and count[b] (DEVICE int64) = the cells that entered
+ * it, for box b < n_box of two FRAME-MAJOR float32 magnitude spectrograms magL, magR [n_frames][pitch] (DEVICE; what par_stft_f32
+ * and par_stft_big_f32 write in mode 1; pitch 0 = bins).  q = float32(L / R) is the correctly rounded float32 quotient; the cells
+ * whose q is not NaN are summed in float64 and counted, a +-inf quotient included, as numpy does; fac = sum / count, NaN when
+ * count == 0 (an empty box, which is how nanmean treats an empty slice, or a box of NaN cells only).  The order of the sum is
+ * fixed -- a frame's cells over 64 lanes and a xor tree, the frames of a box in 256 ascending strided runs, a xor tree and four
+ * partials in order -- and no atomics are used: two runs are bit-identical.  Nothing but fac[0 .. n_box), count[0 .. n_box) and
+ * scratch is written.  Null pointers, sizes < 1, pitch < bins, a scratch that is not 16-byte aligned, a box outside the
+ * spectrogram: PAR_ERR_ARG; scratch_bytes below par_pan_ratio_scratch_bytes: PAR_ERR_WORKSPACE; all before any device call. */
+int par_pan_ratio_f32(int device, const float* magL, const float* magR, int64_t n_frames, int64_t bins, int64_t pitch,
+                      const int32_t* boxes, const int32_t* boxes_host, int64_t n_box, double* fac, int64_t* count, void* scratch,
+                      size_t scratch_bytes, void* stream);
+/* The same fac and count straight from the two channels: xL, xR (DEVICE f32, n samples each at the common element stride x_stride;
+ * an interleaved stereo file is xR == xL + 1 with x_stride == 2, whose samples then arrive as one 8-byte load per L/R pair;
+ * planar channels and wider strides work too).  Padding, framing, scaling and the float32 magnitude are those of par_stft_f32 mode
+ * 1 on each channel, bins = n_fft*zeropad/2 + 1 and n_frames = par_stft_frames(n, n_fft, hop); only frames inside a box are
+ * transformed (a frame inside k boxes k times), and no spectrogram is stored.  The quotients, their float64 sums per (box, frame)
+ * and the reduction over a box's frames are par_pan_ratio_f32's, the order inside a frame differs (the lanes own bins as the
+ * transform leaves them).  Bit-identical from run to run.  n_fft*zeropad must be a power of two in [16, 16384], otherwise
+ * PAR_ERR_UNSUPPORTED (compose par_stft_big_f32 mode 1 twice and par_pan_ratio_f32).  Errors as par_pan_ratio_f32.
+ * par_stft_pan_scratch_bytes == par_pan_ratio_scratch_bytes (one layout). */
+size_t par_stft_pan_scratch_bytes(const int32_t* boxes_host, int64_t n_box);
+int par_stft_pan_ratio_f32(int device, const float* xL, const float* xR, int64_t x_stride, int64_t n, int n_fft, int hop, int zeropad,
+                           const float* window, const int32_t* boxes, const int32_t* boxes_host, int64_t n_box, double* fac,
+                           int64_t* count, void* scratch, size_t scratch_bytes, void* stream);
+/* out[i * out_stride] = float32(float64(sig[i * sig_stride]) * np.interp(i, xp, fp)), i < n (DEVICE f32 in and out, channel views
+ * of interleaved arrays; xp, fp DEVICE f64[m], xp non-decreasing): run_resample's `signal[:, 1] * af` as the FLOAT file stores it.
+ * np.interp's arithmetic is restated operation by operation (the interpolation step of par_lag_to_pos_f64): equal to numpy bit for
+ * bit, fp[0] before the first knot and fp[m-1] behind the last, fp[j] exactly on a knot (the last of equal knots), NaN and inf in
+ * fp or sig propagating as numpy's.  m == 1 is a constant gain.  n == 0: PAR_OK, nothing done.  Null pointers, m < 1 (np.interp
+ * raises ValueError), n < 0, a stride < 1: PAR_ERR_ARG before any device call. */
+int par_pan_apply_f32(int device, const float* sig, int64_t sig_stride, int64_t n, const double* xp, const double* fp, int64_t m,
+                      float* out, int64_t out_stride, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli humspeed --hum 50 --resample tape.wav              # -> tape_resampled_<percent>.wav
     python -m pyaudiorestoration_amd.cli dynamics remaster.flac original.flac               # -> remaster.flacdecompressed.wav
     python -m pyaudiorestoration_amd.cli azimuth take.tapesync --ref take1.flac --box 12,300,22,3000 --out take2.tapesync
+    python -m pyaudiorestoration_amd.cli pan tape.pan                                       # stereo balance project -> tape_out.wav
+    python -m pyaudiorestoration_amd.cli pan --box 12,300,14,5000 --fft 4096 --overlap 8 tape.wav --out tape.pan --apply
 """
 import argparse
 import json
@@ -211,7 +213,41 @@ def parser():
     z.add_argument("--reject", type=float, default=0.1, help="lags whose |correlation| is below this are interpolated over")
     z.add_argument("--ignore-phase", action="store_true", help="correlate on |.|")
     z.add_argument("--out", default=None, metavar="PROJECT2", help="write the project with the line appended (default: only log)")
+    w = sub.add_parser("pan", help="stereo balance (pypan): apply a .pan project, or measure L/R boxes and append them to one")
+    w.add_argument("file", metavar="FILE", help="a .pan JSON written by the GUI or by --out (applied), or the stereo file to measure")
+    w.add_argument("--box", action="append", type=pair, default=[], help="T0,F0,T1,F1 (s, Hz): a box to measure; may be repeated")
+    w.add_argument("--fft", type=int, default=4096, help="FFT size of the measurement")
+    w.add_argument("--overlap", type=int, default=8, help="hop = fft / overlap")
+    w.add_argument("--zeropad", type=int, default=1, help="zero-padding factor of the measurement")
+    w.add_argument("--out", default=None, metavar="PROJECT", help="append the measured markers to this .pan project (created if missing)")
+    w.add_argument("--apply", action="store_true", help="after measuring, also write <stem>_out.wav (a project is always applied)")
+    w.add_argument("--keep-left", action="store_true", help="extension: write a stereo file with the untouched left channel")
     return ap
+
+
+def _pan(args):
+    from . import pypan
+    if any(len(b) != 4 for b in args.box):
+        raise SystemExit("--box takes T0,F0,T1,F1")
+    if args.file.lower().endswith(pypan.EXT):
+        if args.box:
+            raise SystemExit("--box measures an audio file; give the project to extend with --out")
+        written, _ = pypan.process(project=args.file, keep_left=args.keep_left)
+    else:
+        if not args.box:
+            raise SystemExit("nothing to do: give --box to measure, or a .pan project to apply")
+        cfg = {"fft_size": args.fft, "fft_overlap": args.overlap, "fft_zeropad": args.zeropad, "source": args.file, "markers": []}
+        if args.out and os.path.exists(args.out):
+            cfg = json.load(open(args.out))
+        written, markers = pypan.process(args.file, project=cfg, boxes=args.box, keep_left=args.keep_left, apply=args.apply)
+        for m in markers[len(cfg.get("markers", ())):]:
+            logging.info("%s: box %s .. %s: L/R = %.9g", args.file, m.a, m.b, m.pan)
+        if args.out:
+            pypan.save_project(args.out, dict(cfg, markers=markers))
+            logging.info("wrote %s", args.out)
+    if written:
+        logging.info("wrote %s", written)
+    return 0
 
 
 def main(argv=None):
@@ -233,6 +269,8 @@ def main(argv=None):
         if args.out:
             logging.info("wrote %s", args.out)
         return 0
+    if args.cmd == "pan":                       # one file, one GPU
+        return _pan(args)
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()
     for f in sorted(args.files, key=lambda p: -os.path.getsize(p)):     # longest first

@@ -14,7 +14,7 @@ void set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int par_version(void) { return 109; }     // 109: harmonic / percussive separation (par_hpss_f32, par_residual_f32), and added at 109 without a bump: fixed-ratio resampling (par_resample_fixed_out_len, par_resample_fixed_f32) and the renoiser's offset gauge (par_gauge_frames, par_gauge_scratch_bytes, par_gauge_offset_f32); 108: the renoiser's noise-floor gate (par_gate_spectrum_f32, par_gate_stft_f32, par_gate_stft_transformed_frames, par_mean_mag_frames_f32); 107: the Spectral Expander and averaged spectra (par_stft_band_db_f32, par_mean_db_frames_f32, par_uniform_filter_nearest_f64, par_expand_gain_f32, par_sum_rows_f64_f32, par_normalize_f32); 106 (r06): par_varispeed_fused_batch_f32 (several files per launch); 105 (r06): par_fused_redo_list; par_speed_to_pos_fill_fused NaN-fills from a plan without checkpoints (lazy / not fused_ok); the mono streaming launch is two kernels by stream kind (k_sinc_pipe<1, 2>, <1, 1>); 104 (r05): stereo form of the streaming kernel (interleaved NT = 32 files), end tiles inside the streaming launch; 103 (r05): lazy plans (fused_ok 2, force_host | 8), the streaming kernel is par_varispeed_fused_f32's default for mono NT = 32 (par_varispeed_fused_alone_f32 is gone), par_sosfiltfilt_batch_f64
+int par_version(void) { return 109; }     // 109: harmonic / percussive separation (par_hpss_f32, par_residual_f32), and added at 109 without a bump: fixed-ratio resampling (par_resample_fixed_out_len, par_resample_fixed_f32) and the renoiser's offset gauge (par_gauge_frames, par_gauge_scratch_bytes, par_gauge_offset_f32) and the stereo balance tool (par_pan_ratio_scratch_bytes, par_pan_ratio_f32, par_stft_pan_scratch_bytes, par_stft_pan_ratio_f32, par_pan_apply_f32); 108: the renoiser's noise-floor gate (par_gate_spectrum_f32, par_gate_stft_f32, par_gate_stft_transformed_frames, par_mean_mag_frames_f32); 107: the Spectral Expander and averaged spectra (par_stft_band_db_f32, par_mean_db_frames_f32, par_uniform_filter_nearest_f64, par_expand_gain_f32, par_sum_rows_f64_f32, par_normalize_f32); 106 (r06): par_varispeed_fused_batch_f32 (several files per launch); 105 (r06): par_fused_redo_list; par_speed_to_pos_fill_fused NaN-fills from a plan without checkpoints (lazy / not fused_ok); the mono streaming launch is two kernels by stream kind (k_sinc_pipe<1, 2>, <1, 1>); 104 (r05): stereo form of the streaming kernel (interleaved NT = 32 files), end tiles inside the streaming launch; 103 (r05): lazy plans (fused_ok 2, force_host | 8), the streaming kernel is par_varispeed_fused_f32's default for mono NT = 32 (par_varispeed_fused_alone_f32 is gone), par_sosfiltfilt_batch_f64
 
 int par_device_count(void) {
   int n = 0;

@@ -18,6 +18,7 @@
 #include "par_common.h"
 #include "db_math.h"
 #include "np_abs.h"
+#include "pan_items.h"
 #include <math.h>
 #include <map>
 #include <set>
@@ -401,6 +402,173 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __
       }
     }
     if (live && j == 0) reinterpret_cast<double*>(out)[fr] = band_acc / (double)(band_u - band_l);
+  }
+}
+
+// ---- stereo balance boxes straight from the two channels (pypan_gui.py:79-103) ------------------------------------------
+// One frame slot of FftGeom per work item (box, frame) of pan_items.h.  The slot's lanes gather the frame of BOTH channels
+// in one pass over the samples (PAIR: an interleaved stereo file, xR == xL + 1 and x_stride == 2, delivers L and R of a
+// sample in one 8-byte load), transform L, keep the float32 magnitudes of the bins they own in registers, transform R
+// through the same LDS frame and divide bin by bin: both magnitudes of a cell meet in the lane that owns the bin, so the
+// quotient needs no exchange.  Each lane sums its quotients inside the band in float64 and counts them; the slot reduces as
+// k_stft mode 2 does (xor butterflies, then the waves' partials in wave order) and writes ONE PanPart.  No spectrogram
+// reaches HBM, and frames outside every box are never transformed.  Gather, window product, transform, untangle and the
+// magnitude are k_stft mode 1's expressions, operation by operation.
+template <int LOGH, bool PAIR>
+__global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft_pan(const float* __restrict__ xL, const float* __restrict__ xR,
+                                                                      int64_t n, int64_t x_stride, int n_fft, int hop,
+                                                                      const float* __restrict__ window,
+                                                                      const float2* __restrict__ tw, const float2* __restrict__ post,
+                                                                      const int* __restrict__ boxes, int64_t n_box,
+                                                                      const int64_t* __restrict__ offs, PanPart* __restrict__ part,
+                                                                      int64_t n_items, float scale) {
+  using G = FftGeom<LOGH>;
+  constexpr int H = G::H, T = G::T;
+  extern __shared__ __attribute__((aligned(16))) float2 lds[];
+  const int f = threadIdx.x / T, j = threadIdx.x - f * T;
+  float2* X = lds + f * G::FrameLds;
+  const int64_t item = xcd_contiguous_block((n_items + G::Frames - 1) / G::Frames) * G::Frames + f;
+  const bool live = item < n_items;            // a dead slot runs along with zeros (the transforms synchronise the workgroup)
+  int band_l = 0, band_u = 0;
+  long long fr = 0;
+  if (live) {
+    const int64_t box = pan_item_box(offs, n_box, item);
+    const int* bx = boxes + 4 * box;
+    band_l = bx[0];
+    band_u = bx[1];
+    fr = (long long)bx[2] + (item - offs[box]);
+  }
+  // one (L, R) pair per sample index
+  auto sample = [&](long long idx) {
+    if constexpr (PAIR) return *reinterpret_cast<const float2*>(xL + 2 * idx);
+    else return make_float2(xL[idx * x_stride], xR[idx * x_stride]);
+  };
+  float2 vL[8], vR[8];
+  const long long base = fr * hop - (n_fft >> 1);
+  const bool interior = live && base >= 0 && base + n_fft <= (long long)n;
+  if (interior && n_fft == 2 * H) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t0 = 2 * (j + q * T);
+      const float2 w = *reinterpret_cast<const float2*>(window + t0);
+      const float2 s0 = sample(base + t0), s1 = sample(base + t0 + 1);
+      vL[q] = make_float2(w.x * s0.x, w.y * s1.x);
+      vR[q] = make_float2(w.x * s0.y, w.y * s1.y);
+    }
+  } else if (interior) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t0 = 2 * (j + q * T);
+      float2 zl = make_float2(0.0f, 0.0f), zr = zl;
+      if (t0 + 1 < n_fft) {
+        const float2 w = *reinterpret_cast<const float2*>(window + t0);
+        const float2 s0 = sample(base + t0), s1 = sample(base + t0 + 1);
+        zl = make_float2(w.x * s0.x, w.y * s1.x);
+        zr = make_float2(w.x * s0.y, w.y * s1.y);
+      } else if (t0 < n_fft) {
+        const float w = window[t0];
+        const float2 s0 = sample(base + t0);
+        zl.x = w * s0.x;
+        zr.x = w * s0.y;
+      }
+      vL[q] = zl;
+      vR[q] = zr;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t0 = 2 * (j + q * T);
+      float2 zl = make_float2(0.0f, 0.0f), zr = zl;
+      if (live) {
+        if (t0 < n_fft) {
+          const float w = window[t0];
+          const float2 s0 = sample(reflect_index(base + t0, n));
+          zl.x = w * s0.x;
+          zr.x = w * s0.y;
+        }
+        if (t0 + 1 < n_fft) {
+          const float w = window[t0 + 1];
+          const float2 s1 = sample(reflect_index(base + t0 + 1, n));
+          zl.y = w * s1.x;
+          zr.y = w * s1.y;
+        }
+      }
+      vL[q] = zl;
+      vR[q] = zr;
+    }
+  }
+  constexpr int P = (H / 2) / T;
+  float2 pw[P + 1];
+#pragma unroll
+  for (int i = 0; i < P; ++i) pw[i] = post[j + i * T];
+  pw[P] = post[H / 2];
+  const float hs = 0.5f * scale;
+  constexpr bool kLinearPad = (T % 8) == 0;
+  constexpr int kPadStep = T + T / 8;
+  const int lp_k0 = lpad(j), lp_m0 = lpad(H - j);
+  // k_stft's untangle of the pair (k, H - k), k = j + i T (lane 0 adds the self-paired bin H/2): emit(slot, k, re, im) with the
+  // lane's bins numbered slot = 2 i and 2 i + 1
+  auto untangle = [&](auto&& emit) {
+#pragma unroll
+    for (int i = 0; i <= P; ++i) {
+      const int k = (i < P) ? j + i * T : H / 2;
+      if (i == P && j != 0) break;
+      int sk = lpad(k), sm = lpad((H - k) & (H - 1));
+      if (kLinearPad && i < P) {
+        sk = lp_k0 + i * kPadStep;
+        sm = (i == 0 && j == 0) ? 0 : lp_m0 - i * kPadStep;
+      }
+      const float2 zk = X[sk];
+      const float2 zc = cconj(X[sm]);
+      const float2 ev = cadd(zk, zc);
+      const float2 t = cmul(pw[i], csub(zk, zc));
+      emit(2 * i, k, ev.x + t.y, ev.y - t.x);
+      if (i < P) emit(2 * i + 1, H - k, ev.x - t.y, -ev.y - t.x);
+    }
+  };
+  float magl[2 * P + 1] = {};
+  fft_core<LOGH>(vL, X, j, tw);
+  untangle([&](int slot, int, float re, float im) { magl[slot] = fmaf(__builtin_amdgcn_sqrtf(fmaf(re, re, im * im)), hs, 1e-7f); });
+  // fft_core synchronises the frame's lanes before its first store to X: the reads above are done by then
+  fft_core<LOGH>(vR, X, j, tw);
+  double acc = 0.0;
+  int cnt = 0;
+  untangle([&](int slot, int k, float re, float im) {
+    if (k >= band_l && k < band_u) {
+      const float magr = fmaf(__builtin_amdgcn_sqrtf(fmaf(re, re, im * im)), hs, 1e-7f);
+      const float q = __fdiv_rn(magl[slot], magr);          // numpy's float32 division, correctly rounded
+      if (q == q) {                                          // nanmean skips NaN cells; +-inf is summed
+        acc += (double)q;
+        ++cnt;
+      }
+    }
+  });
+  constexpr int kLanes = T < kWave ? T : kWave;
+#pragma unroll
+  for (int o = kLanes / 2; o > 0; o >>= 1) {
+    acc += __shfl_xor(acc, o, kWave);
+    cnt += __shfl_xor(cnt, o, kWave);
+  }
+  if constexpr (T > kWave) {
+    double* psum = reinterpret_cast<double*>(lds + G::Frames * G::FrameLds) + f * (T / kWave);
+    int* pcnt = reinterpret_cast<int*>(reinterpret_cast<double*>(lds + G::Frames * G::FrameLds) + G::Threads / kWave) + f * (T / kWave);
+    if ((j & (kWave - 1)) == 0) {
+      psum[j / kWave] = acc;
+      pcnt[j / kWave] = cnt;
+    }
+    __syncthreads();
+    if (j == 0) {
+      acc = psum[0];
+      cnt = pcnt[0];
+      for (int w = 1; w < T / kWave; ++w) {
+        acc += psum[w];
+        cnt += pcnt[w];
+      }
+    }
+  }
+  if (live && j == 0) {
+    part[item].sum = acc;
+    part[item].cnt = cnt;
   }
 }
 
@@ -1804,6 +1972,81 @@ int par_stft_band_db_f32(int device, const float* x, int64_t n, int64_t x_stride
   }
 #undef PAR_BAND_LAUNCH
 #undef PAR_BAND_LAUNCH_U
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+// Stereo balance boxes straight from the two channels (k_stft_pan): fac[b], count[b] as par_pan_ratio_f32 gives them on the
+// mode-1 spectrograms of xL and xR, without the spectrograms.
+size_t par_stft_pan_scratch_bytes(const int32_t* boxes_host, int64_t n_box) { return par::pan_scratch_bytes(boxes_host, n_box); }
+
+int par_stft_pan_ratio_f32(int device, const float* xL, const float* xR, int64_t x_stride, int64_t n, int n_fft, int hop, int zeropad,
+                           const float* window, const int32_t* boxes, const int32_t* boxes_host, int64_t n_box, double* fac,
+                           int64_t* count, void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(xL && xR && window && boxes && boxes_host && fac && count && scratch, PAR_ERR_ARG, "par_stft_pan_ratio_f32: null pointer");
+  PAR_REQUIRE(n >= 1 && x_stride >= 1 && hop >= 1 && zeropad >= 1 && n_fft >= 2 && n_box >= 1 && n_box <= kPanMaxBoxes, PAR_ERR_ARG,
+              "par_stft_pan_ratio_f32: bad sizes");
+  PAR_REQUIRE(((uintptr_t)scratch & 15) == 0, PAR_ERR_ARG, "par_stft_pan_ratio_f32: scratch is not 16-byte aligned");
+  const int64_t M64 = (int64_t)n_fft * zeropad;
+  PAR_REQUIRE(M64 >= 16 && M64 <= 16384 && (M64 & (M64 - 1)) == 0 && (n_fft % 2) == 0, PAR_ERR_UNSUPPORTED,
+              "par_stft_pan_ratio_f32: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)M64);
+  const int M = (int)M64, H = M / 2;
+  const int64_t n_frames = par_stft_frames(n, n_fft, hop);
+  int64_t n_items = 0;
+  int rc = pan_check_boxes("par_stft_pan_ratio_f32", boxes_host, n_box, H + 1, n_frames, &n_items);
+  if (rc != PAR_OK) return rc;
+  PAR_REQUIRE(scratch_bytes >= pan_scratch_bytes(boxes_host, n_box), PAR_ERR_WORKSPACE, "par_stft_pan_ratio_f32: scratch %zu < %zu",
+              scratch_bytes, pan_scratch_bytes(boxes_host, n_box));
+  PAR_HIP_CHECK(hipSetDevice(device));
+  Twiddles tw;
+  rc = get_twiddles(device, M, &tw);
+  if (rc != PAR_OK) return rc;
+  hipStream_t s = as_stream(stream);
+  const float scale = (float)(1.0 / sqrt((double)n_fft));
+  const int64_t* offs = reinterpret_cast<const int64_t*>(scratch);
+  PanPart* part = reinterpret_cast<PanPart*>(reinterpret_cast<char*>(scratch) + pan_offs_bytes(n_box));
+  // an interleaved stereo pair: both channels of a sample in one aligned 8-byte load
+  const bool pair = xR == xL + 1 && x_stride == 2 && ((uintptr_t)xL & 7) == 0;
+  launch_pan_offsets(boxes, n_box, scratch, s);
+#define PAR_PAN_LDS(LH) ((size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2) + (size_t)FftGeom<LH>::Threads / kWave * 16)
+#define PAR_PAN_LAUNCH_P(LH, PR)                                                                                               \
+  hipLaunchKernelGGL((k_stft_pan<LH, PR>), dim3((unsigned)(ceil_div(ceil_div(n_items, FftGeom<LH>::Frames), 8) * 8)),            \
+                     dim3(FftGeom<LH>::Threads), PAR_PAN_LDS(LH), s, xL, xR, n, x_stride, n_fft, hop, window, tw.w, tw.post, boxes, \
+                     n_box, offs, part, n_items, scale)
+#define PAR_PAN_LAUNCH(LH)                 \
+  do {                                     \
+    if (pair) PAR_PAN_LAUNCH_P(LH, true);  \
+    else PAR_PAN_LAUNCH_P(LH, false);      \
+  } while (0)
+  if (n_items > 0) {
+    switch (ilog2(H)) {
+      case 3: PAR_PAN_LAUNCH(3); break;
+      case 4: PAR_PAN_LAUNCH(4); break;
+      case 5: PAR_PAN_LAUNCH(5); break;
+      case 6: PAR_PAN_LAUNCH(6); break;
+      case 7: PAR_PAN_LAUNCH(7); break;
+      case 8: PAR_PAN_LAUNCH(8); break;
+      case 9: PAR_PAN_LAUNCH(9); break;
+      case 10: PAR_PAN_LAUNCH(10); break;
+      case 11: PAR_PAN_LAUNCH(11); break;
+      case 12: PAR_PAN_LAUNCH(12); break;
+      case 13: {
+        // 72 KB of LDS, above a kernel's default 64 KB (as k_stft at this size)
+        for (const void* fn : {reinterpret_cast<const void*>(&k_stft_pan<13, true>), reinterpret_cast<const void*>(&k_stft_pan<13, false>)}) {
+          const int rc2 = raise_dynamic_lds(fn, (int)PAR_PAN_LDS(13), device);
+          if (rc2 != PAR_OK) return rc2;
+        }
+        PAR_PAN_LAUNCH(13);
+        break;
+      }
+      default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_pan_ratio_f32: unsupported size");
+    }
+  }
+#undef PAR_PAN_LAUNCH
+#undef PAR_PAN_LAUNCH_P
+#undef PAR_PAN_LDS
+  launch_pan_reduce(n_box, scratch, fac, count, s);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }
