@@ -693,6 +693,27 @@ int par_stft_pan_ratio_f32(int device, const float* xL, const float* xR, int64_t
  * raises ValueError), n < 0, a stride < 1: PAR_ERR_ARG before any device call. */
 int par_pan_apply_f32(int device, const float* sig, int64_t sig_stride, int64_t n, const double* xp, const double* fp, int64_t m,
                       float* out, int64_t out_stride, void* stream);
+/* ---- Differential EQ (difeq_gui.py:24-38 get_eq): time-averaged dB spectra straight from the samples ---------------------------
+ * par_stft_mean_db_scratch_bytes and par_stft_mean_db_f32 are added at ABI 109: par_version() stays 109.
+ *
+ * mean[c][b] (DEVICE f64[n_ch][bins], bins = n_fft*zeropad/2 + 1) = (sum over frames f of 20 log10((double) m_f[b])) / n_frames
+ * for every channel c < n_ch of the interleaved signal x[i * x_stride + c] (DEVICE f32, n samples per channel), where m_f[b] is
+ * the float32 magnitude par_stft_f32 mode 1 writes for that channel (padding, framing, scaling and the repeated reflection of a
+ * signal shorter than n_fft/2 included) and n_frames = par_stft_frames(n, n_fft, hop): np.mean(to_dB(get_mag(x)), axis=1) of
+ * util/spectrum_flat.py:20-24 in float64, for all channels in one launch and with no spectrogram stored.
+ * Order of the sum (fixed by the arguments alone, no atomics, bit-identical from run to run and from device to device): the
+ * frames are cut into runs of R = max(16, ceil(n_frames / 512)) consecutive frames; inside a run the terms of a bin are added in
+ * float64 in ascending frame order starting from 0; the runs' partial sums are added in ascending run order starting from run
+ * 0's; the total is divided by n_frames once.  `scratch` (DEVICE, 8-byte aligned, par_stft_mean_db_scratch_bytes: one float64 row of
+ * bins per run and channel) needs no initialisation; nothing but mean[0 .. n_ch*bins) and scratch is written.  The work runs on
+ * the caller's stream without host synchronisation.  n_fft*zeropad must be a power of two in [16, 16384] (n_fft even), otherwise
+ * PAR_ERR_UNSUPPORTED (compose par_stft_big_f32 mode 1 and par_mean_db_frames_f32).  Null pointers, n, hop, zeropad < 1,
+ * n_fft < 2, n_ch outside 1..8, x_stride < n_ch, misaligned mean or scratch: PAR_ERR_ARG; scratch_bytes too small:
+ * PAR_ERR_WORKSPACE; all before any device call. */
+/* Bytes of DEVICE scratch (host arithmetic; 0 for sizes par_stft_mean_db_f32 does not take) */
+size_t par_stft_mean_db_scratch_bytes(int64_t n, int n_fft, int hop, int zeropad, int n_ch);
+int par_stft_mean_db_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_ch, int n_fft, int hop, int zeropad,
+                         const float* window, double* mean, void* scratch, size_t scratch_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

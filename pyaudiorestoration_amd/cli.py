@@ -20,6 +20,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli azimuth take.tapesync --ref take1.flac --box 12,300,22,3000 --out take2.tapesync
     python -m pyaudiorestoration_amd.cli pan tape.pan                                       # stereo balance project -> tape_out.wav
     python -m pyaudiorestoration_amd.cli pan --box 12,300,14,5000 --fft 4096 --overlap 8 tape.wav --out tape.pan --apply
+    python -m pyaudiorestoration_amd.cli difeq transfer.wav master.wav --out eq.txt         # Differential EQ -> eq.txt, eq_L.txt, eq_R.txt
 """
 import argparse
 import json
@@ -222,7 +223,32 @@ def parser():
     w.add_argument("--out", default=None, metavar="PROJECT", help="append the measured markers to this .pan project (created if missing)")
     w.add_argument("--apply", action="store_true", help="after measuring, also write <stem>_out.wav (a project is always applied)")
     w.add_argument("--keep-left", action="store_true", help="extension: write a stereo file with the untouched left channel")
+    q = sub.add_parser("difeq", help="Differential EQ: the averaged EQ curve that takes every SRC to its REF, as Audacity FilterCurve presets")
+    q.add_argument("files", nargs="+", metavar="SRC REF", help="pairs: the file to equalise, then a transfer of the same recording to match")
+    q.add_argument("--out", required=True, metavar="EQ.txt", help="writes EQ.txt (channel mean), EQ_L.txt and EQ_R.txt")
+    q.add_argument("--channels", default="L+R", choices=("L+R", "L", "R"), help="which channels are analysed")
+    q.add_argument("--highpass", type=int, default=0, help="no influence under this frequency (Hz)")
+    q.add_argument("--rolloff", type=pair, default=[21000, 22000], help="A,B (Hz): full influence up to A, none from B on")
+    q.add_argument("--resolution", type=int, default=200, help="keys of the output curve, 20..2000")
+    q.add_argument("--smoothing", type=int, default=50, help="points of the box average, 1..200")
+    q.add_argument("--strength", type=int, default=100, help="percent")
+    q.add_argument("--keep-gain", action="store_true", help="take the curve's mean gain off, so that the level stays")
     return ap
+
+
+def _difeq(args):
+    from . import difeq
+    if len(args.files) % 2 or len(args.rolloff) != 2:
+        raise SystemExit("difeq takes SRC REF pairs, and --rolloff A,B")
+    if not (20 <= args.resolution <= 2000 and 1 <= args.smoothing <= 200):
+        raise SystemExit("--resolution is 20..2000 and --smoothing 1..200 (the GUI's spin boxes)")
+    pairs = list(zip(args.files[0::2], args.files[1::2]))
+    res = difeq.process(pairs, args.out, args.channels, highpass=args.highpass, rolloff_start=args.rolloff[0], rolloff_end=args.rolloff[1],
+                        resolution=args.resolution, smoothing=args.smoothing, strength=args.strength, keep_gain=args.keep_gain)
+    logging.info("%d pair(s), %d keys, gain %.9g dB", len(pairs), len(res["freqs_av"]), res["gain"])
+    for p in res["paths"]:
+        logging.info("wrote %s", p)
+    return 0
 
 
 def _pan(args):
@@ -271,6 +297,8 @@ def main(argv=None):
         return 0
     if args.cmd == "pan":                       # one file, one GPU
         return _pan(args)
+    if args.cmd == "difeq":                     # pairs of files, one GPU
+        return _difeq(args)
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()
     for f in sorted(args.files, key=lambda p: -os.path.getsize(p)):     # longest first

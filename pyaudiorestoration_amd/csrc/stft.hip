@@ -572,6 +572,148 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft_pan(const float
   }
 }
 
+// ---- time-averaged dB spectra straight from the samples (util/spectrum_flat.py:20-24 under difeq_gui.get_eq) ------------------
+// A frame slot of FftGeom takes a RUN of consecutive frames of one channel: it transforms them one after the other through the
+// same LDS frame and every lane adds 20 log10 of the float32 magnitudes of the bins the untangle step leaves it -- the pairs
+// (k, H - k), k = j + i T, and lane 0 the self-paired bin H/2: at most 9 -- into float64 registers, frames ascending.  After the
+// run the slot writes ONE partial row; k_mean_db_reduce adds the rows in run order and divides by the frame count.  No
+// spectrogram reaches HBM, no atomics, and the run length depends on the frame count alone (mean_run_len), so the order of
+// every sum is fixed by the arguments.  Gather, window product, transform, untangle and the magnitude are k_stft mode 1's
+// expressions, operation by operation.  Every slot of the grid makes `run` passes through fft_core (workgroup barriers for
+// T > 64): a pass beyond the slot's last frame transforms zeros and adds nothing.
+constexpr int kMeanMinRun = 16;        // frames per run for short files: 16 transforms amortise the partial row
+constexpr int kMeanMaxRuns = 512;      // longer files: at most this many partial rows per channel (twice the CUs)
+static inline int64_t mean_run_len(int64_t n_frames) {
+  const int64_t r = (n_frames + kMeanMaxRuns - 1) / kMeanMaxRuns;
+  return r < kMeanMinRun ? kMeanMinRun : r;
+}
+
+template <int LOGH, bool UNIT>
+__global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft_mean(const float* __restrict__ x_all, int64_t n, int64_t x_stride_arg,
+                                                                       int n_fft, int hop, const float* __restrict__ window,
+                                                                       const float2* __restrict__ tw, const float2* __restrict__ post,
+                                                                       double* __restrict__ part, int64_t n_frames, int64_t run,
+                                                                       int64_t n_runs, float scale) {
+  const int64_t x_stride = UNIT ? 1 : x_stride_arg;
+  using G = FftGeom<LOGH>;
+  constexpr int H = G::H, T = G::T;
+  extern __shared__ __attribute__((aligned(16))) float2 lds[];
+  const int f = threadIdx.x / T, j0 = threadIdx.x - f * T;
+  float2* X = lds + f * G::FrameLds;
+  const int c = blockIdx.y;
+  const float* x = x_all + c;
+  const int64_t slot = xcd_contiguous_block((n_runs + G::Frames - 1) / G::Frames) * G::Frames + f;
+  const bool owns = slot < n_runs;             // a slot past the last run goes along with zeros (the transforms synchronise the workgroup)
+  const int64_t f_first = slot * run;
+  const int64_t f_end = !owns ? f_first : (f_first + run < n_frames ? f_first + run : n_frames);
+  constexpr int bins = H + 1, P = (H / 2) / T;
+  float2 pw[P + 1];
+#pragma unroll
+  for (int i = 0; i < P; ++i) pw[i] = post[j0 + i * T];
+  pw[P] = post[H / 2];
+  const float hs = 0.5f * scale;
+  constexpr bool kLinearPad = (T % 8) == 0;
+  constexpr int kPadStep = T + T / 8;
+  double acc[2 * P + 1] = {};
+  for (int64_t r = 0; r < run; ++r) {
+    const int64_t fr = f_first + r;
+    const bool live = fr < f_end;
+    float2 v[8];
+    // A lane of the 1024-lane workgroup has 128 registers.  Everything a pass derives from the lane index alone -- window values,
+    // stage twiddles and their powers, LDS and sample offsets -- would be kept across the loop and spill; an opaque copy of the
+    // index keeps it inside the pass (integer arithmetic and L1 / L2 hits, beside nine float64 logarithms per lane).
+    int j = j0;
+    if constexpr (G::Threads > 512) asm volatile("" : "+v"(j));
+    const int lp_k0 = lpad(j), lp_m0 = lpad(H - j);
+    const long long base = (long long)fr * hop - (n_fft >> 1);
+    const bool interior = live && base >= 0 && base + n_fft <= (long long)n;
+    if (interior && n_fft == 2 * H) {
+      const float* xs = x + base * x_stride;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        const float2 w = *reinterpret_cast<const float2*>(window + t0);
+        v[q] = make_float2(w.x * xs[(int64_t)t0 * x_stride], w.y * xs[(int64_t)(t0 + 1) * x_stride]);
+      }
+    } else if (interior) {
+      const float* xs = x + base * x_stride;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        float2 z = make_float2(0.0f, 0.0f);
+        if (t0 + 1 < n_fft) {
+          const float2 w = *reinterpret_cast<const float2*>(window + t0);
+          z.x = w.x * xs[(int64_t)t0 * x_stride];
+          z.y = w.y * xs[(int64_t)(t0 + 1) * x_stride];
+        } else if (t0 < n_fft) {
+          z.x = window[t0] * xs[(int64_t)t0 * x_stride];
+        }
+        v[q] = z;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        float2 z = make_float2(0.0f, 0.0f);
+        if (live) {
+          if (t0 < n_fft) z.x = window[t0] * x[reflect_index(base + t0, n) * x_stride];
+          if (t0 + 1 < n_fft) z.y = window[t0 + 1] * x[reflect_index(base + t0 + 1, n) * x_stride];
+        }
+        v[q] = z;
+      }
+    }
+    // fft_core synchronises the frame's lanes before its first store to X: the previous frame's untangle reads are done by then
+    fft_core<LOGH>(v, X, j, tw);
+    if (live) {
+      // the float32 magnitudes first (the LDS reads and the untangle), then the float64 logarithms
+      float mg[2 * P + 1];
+      auto add = [&](int s, float re, float im) { mg[s] = fmaf(__builtin_amdgcn_sqrtf(fmaf(re, re, im * im)), hs, 1e-7f); };
+#pragma unroll
+      for (int i = 0; i <= P; ++i) {
+        const int k = (i < P) ? j + i * T : H / 2;
+        if (i == P && j != 0) break;
+        int sk = lpad(k), sm = lpad((H - k) & (H - 1));
+        if (kLinearPad && i < P) {
+          sk = lp_k0 + i * kPadStep;
+          sm = (i == 0 && j == 0) ? 0 : lp_m0 - i * kPadStep;
+        }
+        const float2 zk = X[sk];
+        const float2 zc = cconj(X[sm]);
+        const float2 ev = cadd(zk, zc);
+        const float2 t = cmul(pw[i], csub(zk, zc));
+        add(2 * i, ev.x + t.y, ev.y - t.x);                     // bin k
+        if (i < P) add(2 * i + 1, ev.x - t.y, -ev.y - t.x);     // bin H - k
+      }
+#pragma unroll
+      for (int s = 0; s <= 2 * P; ++s) {
+        if (s == 2 * P && j != 0) break;
+        acc[s] += 20.0 * log10_pos((double)mg[s]);
+      }
+    }
+  }
+  if (!owns) return;
+  double* row = part + ((int64_t)c * n_runs + slot) * bins;
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    row[j0 + i * T] = acc[2 * i];
+    row[H - (j0 + i * T)] = acc[2 * i + 1];
+  }
+  if (j0 == 0) row[H / 2] = acc[2 * P];
+}
+
+// mean[c][b] = (part[c][0][b] + part[c][1][b] + ... in run order) / n_frames
+__global__ __launch_bounds__(256) void k_mean_db_reduce(const double* __restrict__ part, int64_t n_runs, int bins, int64_t n_frames,
+                                                        double* __restrict__ mean) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= bins) return;
+  const int c = blockIdx.y;
+  const double* p = part + (int64_t)c * n_runs * bins + b;
+  double s = p[0];
+#pragma unroll 8
+  for (int64_t r = 1; r < n_runs; ++r) s += p[r * bins];
+  mean[(int64_t)c * bins + b] = s / (double)n_frames;
+}
+
 // ---- transforms above 8192 points: four-step FFT ----------------------------------------------------------
 // The GUI offers FFT sizes up to 2^20 (util/widgets.py:333-349).  A frame of M = n_fft*zeropad real points is an
 // H = M/2-point complex sequence; H = N1 N2 is transformed in two passes over HBM around the register/LDS core:
@@ -2047,6 +2189,83 @@ int par_stft_pan_ratio_f32(int device, const float* xL, const float* xR, int64_t
 #undef PAR_PAN_LAUNCH_P
 #undef PAR_PAN_LDS
   launch_pan_reduce(n_box, scratch, fac, count, s);
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+// Time-averaged dB spectra of all channels straight from the samples (k_stft_mean + k_mean_db_reduce): what
+// par_mean_db_frames_f32 sums over the mode-1 spectrogram of each channel, divided by the frame count, without the spectrogram.
+static bool stft_mean_supported(int n_fft, int zeropad) {
+  const int64_t M = (int64_t)n_fft * zeropad;
+  return n_fft >= 2 && zeropad >= 1 && (n_fft % 2) == 0 && M >= 16 && M <= 16384 && (M & (M - 1)) == 0;
+}
+
+size_t par_stft_mean_db_scratch_bytes(int64_t n, int n_fft, int hop, int zeropad, int n_ch) {
+  if (n < 1 || hop < 1 || n_ch < 1 || n_ch > 8 || !stft_mean_supported(n_fft, zeropad)) return 0;
+  const int64_t n_frames = par_stft_frames(n, n_fft, hop);
+  const int64_t n_runs = par::ceil_div(n_frames, par::mean_run_len(n_frames));
+  return (size_t)n_ch * (size_t)n_runs * (size_t)((int64_t)n_fft * zeropad / 2 + 1) * sizeof(double);
+}
+
+int par_stft_mean_db_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_ch, int n_fft, int hop, int zeropad,
+                         const float* window, double* mean, void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(x && window && mean && scratch, PAR_ERR_ARG, "par_stft_mean_db_f32: null pointer");
+  PAR_REQUIRE(n >= 1 && hop >= 1 && zeropad >= 1 && n_fft >= 2 && n_ch >= 1 && n_ch <= 8 && x_stride >= n_ch, PAR_ERR_ARG,
+              "par_stft_mean_db_f32: bad sizes (n %lld, n_fft %d, hop %d, zeropad %d, channels %d, stride %lld)", (long long)n, n_fft, hop,
+              zeropad, n_ch, (long long)x_stride);
+  PAR_REQUIRE(((uintptr_t)scratch & 7) == 0 && ((uintptr_t)mean & 7) == 0, PAR_ERR_ARG, "par_stft_mean_db_f32: mean or scratch is not 8-byte aligned");
+  PAR_REQUIRE(stft_mean_supported(n_fft, zeropad), PAR_ERR_UNSUPPORTED,
+              "par_stft_mean_db_f32: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)n_fft * zeropad);
+  const size_t need = par_stft_mean_db_scratch_bytes(n, n_fft, hop, zeropad, n_ch);
+  PAR_REQUIRE(scratch_bytes >= need, PAR_ERR_WORKSPACE, "par_stft_mean_db_f32: scratch %zu < %zu", scratch_bytes, need);
+  const int M = n_fft * zeropad, H = M / 2;
+  const int64_t n_frames = par_stft_frames(n, n_fft, hop);
+  const int64_t run = mean_run_len(n_frames), n_runs = ceil_div(n_frames, run);
+  PAR_HIP_CHECK(hipSetDevice(device));
+  Twiddles tw;
+  int rc = get_twiddles(device, M, &tw);
+  if (rc != PAR_OK) return rc;
+  hipStream_t s = as_stream(stream);
+  const float scale = (float)(1.0 / sqrt((double)n_fft));
+  double* part = reinterpret_cast<double*>(scratch);
+#define PAR_MEAN_LDS(LH) ((size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2))
+#define PAR_MEAN_LAUNCH_U(LH, UN)                                                                                              \
+  hipLaunchKernelGGL((k_stft_mean<LH, UN>), dim3((unsigned)(ceil_div(ceil_div(n_runs, FftGeom<LH>::Frames), 8) * 8), (unsigned)n_ch), \
+                     dim3(FftGeom<LH>::Threads), PAR_MEAN_LDS(LH), s, x, n, x_stride, n_fft, hop, window, tw.w, tw.post, part,   \
+                     n_frames, run, n_runs, scale)
+#define PAR_MEAN_LAUNCH(LH)                         \
+  do {                                              \
+    if (x_stride == 1) PAR_MEAN_LAUNCH_U(LH, true); \
+    else PAR_MEAN_LAUNCH_U(LH, false);              \
+  } while (0)
+  switch (ilog2(H)) {
+    case 3: PAR_MEAN_LAUNCH(3); break;
+    case 4: PAR_MEAN_LAUNCH(4); break;
+    case 5: PAR_MEAN_LAUNCH(5); break;
+    case 6: PAR_MEAN_LAUNCH(6); break;
+    case 7: PAR_MEAN_LAUNCH(7); break;
+    case 8: PAR_MEAN_LAUNCH(8); break;
+    case 9: PAR_MEAN_LAUNCH(9); break;
+    case 10: PAR_MEAN_LAUNCH(10); break;
+    case 11: PAR_MEAN_LAUNCH(11); break;
+    case 12: PAR_MEAN_LAUNCH(12); break;
+    case 13: {
+      // 72 KB of LDS, above a kernel's default 64 KB (as k_stft at this size)
+      for (const void* fn : {reinterpret_cast<const void*>(&k_stft_mean<13, true>), reinterpret_cast<const void*>(&k_stft_mean<13, false>)}) {
+        const int rc2 = raise_dynamic_lds(fn, (int)PAR_MEAN_LDS(13), device);
+        if (rc2 != PAR_OK) return rc2;
+      }
+      PAR_MEAN_LAUNCH(13);
+      break;
+    }
+    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_mean_db_f32: unsupported size");
+  }
+#undef PAR_MEAN_LAUNCH
+#undef PAR_MEAN_LAUNCH_U
+#undef PAR_MEAN_LDS
+  const int bins = H + 1;
+  hipLaunchKernelGGL(k_mean_db_reduce, dim3((unsigned)ceil_div(bins, 256), (unsigned)n_ch), dim3(256), 0, s, part, n_runs, bins, n_frames, mean);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }
