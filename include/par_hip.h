@@ -714,6 +714,42 @@ int par_pan_apply_f32(int device, const float* sig, int64_t sig_stride, int64_t 
 size_t par_stft_mean_db_scratch_bytes(int64_t n, int n_fft, int hop, int zeropad, int n_ch);
 int par_stft_mean_db_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_ch, int n_fft, int hop, int zeropad,
                          const float* window, double* mean, void* scratch, size_t scratch_bytes, void* stream);
+/* ---- Cyclic wow (experiments/cyclic_wow.py): pilot-tone track straight from the samples, fold at candidate cycle lengths -------
+ * par_stft_track_peak_f64 and par_cycle_fold_f64 are added at ABI 109: par_version() stays 109.
+ *
+ * par_stft_track_peak_f64: freqs[i] (DEVICE f64[count]; in = the sampled trail, out = the traced frequency in Hz) for the frames
+ * frame_0 + i, i < count, of the signal x[k * x_stride] (DEVICE f32, n samples): what par_track_peak_f64 writes for the same
+ * frame_0 / count / freqs / sr / tolerance_oct / mode on the spectrogram par_stft_f32 mode 1 stores for x, bit for bit, without
+ * the spectrogram.  Every value the tracker compares is the float32 magnitude m_f[b] of that spectrogram (padding, framing,
+ * scaling and the repeated reflection of a signal shorter than n_fft/2 included) for db = 0, and for db = 1 its float32 dB,
+ * (float)(20 log10((double) m_f[b])) with the float64 logarithm of par_band_mean_db_f32 (|error| <= 1e-15 against numpy's log10):
+ * the float32 dB spectrogram experiments/cyclic_wow.py:34-37 hands PeakTracker.  Per frame: the band [NL, NU) of
+ * par_track_peak_f64 (mode 0: around freqs[i]; mode 1: around freqs[0], read before the launch, the tolerance halved for i > 2),
+ * the first maximum of the band (a NaN never wins; a NaN on bin NL keeps bin NL), is_peak on its two neighbours (bin 0 reads bin
+ * bins - 1 as its left one), parabolic() in float64, bin / (n_fft*zeropad) * sr.  No sum is formed: the result does not depend on
+ * the launch shape and is bit-identical from run to run.  status (DEVICE int32) and its errors are par_track_peak_f64's: an empty
+ * band PAR_ERR_EMPTY_BAND (that frame's freqs entry is left as it was), a peak on the last bin PAR_ERR_INDEX, a band past the last
+ * bin PAR_ERR_SHAPE; these come from a completed launch.  Nothing but freqs[0 .. count) and status is written.  Synchronises (it
+ * returns the status).  count == 0: PAR_OK, nothing done.  n_fft*zeropad must be a power of two in [16, 16384] (n_fft even),
+ * otherwise PAR_ERR_UNSUPPORTED (compose par_stft_big_f32 mode 1 and par_track_peak_f64).  Null pointers, n, hop, zeropad or
+ * x_stride < 1, n_fft < 2, count < 0, frame_0 < 0, frame_0 + count > par_stft_frames(n, n_fft, hop), mode or db outside 0..1:
+ * PAR_ERR_ARG; all argument errors before any device call. */
+int par_stft_track_peak_f64(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, int zeropad,
+                            const float* window, int64_t frame_0, int64_t count, double* freqs, double sr,
+                            double tolerance_oct, int mode, int db, int32_t* status, void* stream);
+/* par_cycle_fold_f64: for every candidate cycle length P = p_first + c, c < n_cand, the track v (DEVICE f64[count]) is cut into
+ * V = count / P whole views (integer division; the frames behind V * P are dropped) and averaged over the views:
+ *   avg[c * avg_pitch + p] = (v[p] + v[P + p] + ... + v[(V - 1) P + p]) / V,  p < P
+ * the sum in float64 in ascending view order starting from view 0, then one division: np.mean(np.split(v[:V * P], V), axis=0)
+ * of get_avg (experiments/cyclic_wow.py:9-27), equal to numpy bit for bit for P >= 2 (numpy reduces the outer axis of a
+ * C-contiguous array row after row).  At P == 1 numpy folds the (V, 1) array into one contiguous run and sums it pairwise; the
+ * order here stays as stated and the two differ by at most 2 (V - 1) 2^-53 sum|v| / V.  delta[c] (DEVICE f64[n_cand]) = max_p avg - min_p avg; a NaN in a row makes its delta NaN, as np.max /
+ * np.min propagate it.  avg (DEVICE f64) may be null; otherwise only avg[c * avg_pitch + 0 .. P) is written, avg_pitch >=
+ * p_first + n_cand - 1.  No atomics: bit-identical from run to run.  The work runs on the caller's stream without host
+ * synchronisation.  Null v or delta, p_first < 1, n_cand < 1, count < 0, p_first + n_cand - 1 > count (the reference's np.split
+ * into zero sections raises), avg_pitch below the longest cycle: PAR_ERR_ARG before any device call. */
+int par_cycle_fold_f64(int device, const double* v, int64_t count, int p_first, int n_cand, double* avg, int64_t avg_pitch,
+                       double* delta, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,9 @@ SIGNATURES = {
     "par_pan_apply_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "par_stft_mean_db_scratch_bytes": (c_sz, [c_i64, c_int, c_int, c_int, c_int]),
     "par_stft_mean_db_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "par_stft_track_peak_f64": (c_int, [c_int, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_dbl, c_dbl,
+                                        c_int, c_int, c_vp, c_vp]),
+    "par_cycle_fold_f64": (c_int, [c_int, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
 }
 HPSS_COMPONENTS, HPSS_MASKS, HPSS_HARMONIC, HPSS_MEDIANS = 0, 1, 2, 3      # par_hpss_f32's out_kind (PAR_HPSS_*)
 NORMALIZE_SCRATCH_BYTES = 4096      # PAR_NORMALIZE_SCRATCH_BYTES

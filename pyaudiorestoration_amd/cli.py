@@ -21,6 +21,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli pan tape.pan                                       # stereo balance project -> tape_out.wav
     python -m pyaudiorestoration_amd.cli pan --box 12,300,14,5000 --fft 4096 --overlap 8 tape.wav --out tape.pan --apply
     python -m pyaudiorestoration_amd.cli difeq transfer.wav master.wav --out eq.txt         # Differential EQ -> eq.txt, eq_L.txt, eq_R.txt
+    python -m pyaudiorestoration_amd.cli cyclic side_a.wav --rpm 33.333 --pilot 3150 --resample   # cyclic wow of a pilot tone -> side_a_res.wav
 """
 import argparse
 import json
@@ -233,6 +234,18 @@ def parser():
     q.add_argument("--smoothing", type=int, default=50, help="points of the box average, 1..200")
     q.add_argument("--strength", type=int, default=100, help="percent")
     q.add_argument("--keep-gain", action="store_true", help="take the curve's mean gain off, so that the level stays")
+    k = sub.add_parser("cyclic", help="cyclic wow analysis: the wow of an off-centre or warped record, measured from a pilot tone")
+    k.add_argument("files", nargs="+")
+    k.add_argument("--rpm", type=float, default=45.0, help="nominal rotation: the search starts at its cycle length")
+    k.add_argument("--pilot", type=float, default=700.0, help="frequency of the pilot tone (Hz)")
+    k.add_argument("--tolerance", type=float, default=0.1, help="cycle lengths within this share of the nominal one are tried")
+    k.add_argument("--tolerance-st", type=float, default=10, help="half width of the tracker's band (semitones)")
+    k.add_argument("--fft", type=int, default=16384, help="FFT size")
+    k.add_argument("--hop", type=int, default=None, help="hop (default: fft / 128)")
+    k.add_argument("--channels", default="L", choices=("L", "R"), help="the channel the pilot is traced in")
+    k.add_argument("--json", default=None, metavar="REPORT.json", help="write the figures (a list when several files are given)")
+    k.add_argument("--resample", action="store_true", help="remove the measured cycle: <stem>_res.wav through the sinc resampler")
+    k.add_argument("--quality", type=int, default=50, help="sinc_quality (NT) of --resample")
     return ap
 
 
@@ -248,6 +261,30 @@ def _difeq(args):
     logging.info("%d pair(s), %d keys, gain %.9g dB", len(pairs), len(res["freqs_av"]), res["gain"])
     for p in res["paths"]:
         logging.info("wrote %s", p)
+    return 0
+
+
+def _cyclic(args):
+    from . import cyclic_wow, io_ops, resampling
+    reports = []
+    for path in args.files:
+        signal, sr, _ = io_ops.read_file(path)
+        hop = cyclic_wow.default_hop(args.fft) if args.hop is None else args.hop
+        res = cyclic_wow.analyse(signal, sr, args.rpm, args.pilot, args.tolerance, args.tolerance_st, args.fft, hop, args.channels)
+        rep = dict(cyclic_wow.report(res), file=path, sr=sr, fft_size=args.fft, hop=hop)
+        logging.info("%s: best cycle length %d frames of %d samples: %.9g s (nominal %.9g s), the record was playing at %.6f rpm", path,
+                     rep["frames_per_rotation"], hop, rep["cycle_duration_s"], 60.0 / args.rpm, rep["rpm_measured"])
+        logging.info("%s: depth of the cycle %.6g octaves = %.6g semitones peak to peak", path, rep["delta_octaves"], rep["delta_semitones"])
+        if args.resample:
+            resampling.run((path,), signal_data=((signal, sr),), speed_curve=cyclic_wow.speed_curve(res, sr, hop), resampling_mode="Sinc",
+                           sinc_quality=args.quality)
+            rep["resampled"] = f"{os.path.splitext(path)[0]}_res.wav"
+            logging.info("wrote %s", rep["resampled"])
+        reports.append(rep)
+    if args.json:
+        with open(args.json, "w") as out:
+            json.dump(reports[0] if len(reports) == 1 else reports, out, indent=1)
+        logging.info("wrote %s", args.json)
     return 0
 
 
@@ -299,6 +336,8 @@ def main(argv=None):
         return _pan(args)
     if args.cmd == "difeq":                     # pairs of files, one GPU
         return _difeq(args)
+    if args.cmd == "cyclic":                    # file after file, one GPU
+        return _cyclic(args)
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()
     for f in sorted(args.files, key=lambda p: -os.path.getsize(p)):     # longest first

@@ -19,6 +19,7 @@
 #include "db_math.h"
 #include "np_abs.h"
 #include "pan_items.h"
+#include "track_band.h"
 #include <math.h>
 #include <map>
 #include <set>
@@ -712,6 +713,182 @@ __global__ __launch_bounds__(256) void k_mean_db_reduce(const double* __restrict
 #pragma unroll 8
   for (int64_t r = 1; r < n_runs; ++r) s += p[r * bins];
   mean[(int64_t)c * bins + b] = s / (double)n_frames;
+}
+
+// ---- Peak / Peak Track straight from the samples (util/wow_detection.py:294-327 on the frames of util/fourier.py:37-75) --------
+// One frame slot of FftGeom per traced frame frame_0 + i, i < count.  Gather, window product, transform, untangle and the
+// magnitude are k_stft mode 1's expressions, operation by operation, so every value the tracker sees is the float32 that
+// par_stft_f32 mode 1 would have stored for that frame (DB: its float32 dB, (float)(20 log10 of the float64 of it), what
+// experiments/cyclic_wow.py:34-37 hands PeakTracker).  The untangle leaves a lane the pairs (k, H - k), k = j + i T (lane 0 also
+// H/2), as documented above k_stft_mean.  Lane 0 of the slot works out the band [NL, NU) before the transform and leaves it in
+// LDS beside the frames (the transform's exchanges publish it).  Behind the barrier that ends the untangle reads the lanes
+// deposit the values of bins NL - 1 .. NU (and of bin bins - 1 for a band that starts on bin 0, whose left neighbour it is) into
+// the frame's own LDS slot, as floats indexed by bin.  Lane j then walks bins NL + j, NL + j + T, ... upwards keeping the first
+// maximum, the slot's lanes reduce (value, bin) pairs to the smaller bin on equal values -- xor butterflies inside a wave for
+// T <= 64, then (T > 64) the waves' pairs through LDS -- and lane 0 finishes with peak_refine (track_band.h), the expression
+// K_track evaluates on a stored spectrogram.  A NaN never wins a comparison, as in K_track's walk; a NaN on bin NL keeps bin NL.
+// A slot past `count` goes along with zeros through every barrier and writes nothing.
+template <int LOGH, bool UNIT>
+__global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft_peak(const float* __restrict__ x, int64_t n, int64_t x_stride_arg,
+                                                                       int n_fft, int hop, const float* __restrict__ window,
+                                                                       const float2* __restrict__ tw, const float2* __restrict__ post,
+                                                                       int64_t frame_0, int64_t count, double* __restrict__ freqs,
+                                                                       double centre, double sr, double tol, int mode, int db,
+                                                                       int* __restrict__ status, float scale) {
+  const int64_t x_stride = UNIT ? 1 : x_stride_arg;
+  using G = FftGeom<LOGH>;
+  constexpr int H = G::H, T = G::T;
+  constexpr int bins = H + 1, P = (H / 2) / T;
+  constexpr int kWaves = T > kWave ? T / kWave : 1;           // waves per frame
+  extern __shared__ __attribute__((aligned(16))) float2 lds[];
+  const int f = threadIdx.x / T, j = threadIdx.x - f * T;
+  float2* X = lds + f * G::FrameLds;
+  // beside the frames: per frame the band (NL, NU, past_end, unused), then per wave of the frame one (value, bin) pair
+  int* side = reinterpret_cast<int*>(lds + G::Frames * G::FrameLds) + f * (4 + 2 * kWaves);
+  const int64_t slot = xcd_contiguous_block((count + G::Frames - 1) / G::Frames) * G::Frames + f;
+  const bool live = slot < count;
+  const int64_t fr = frame_0 + slot;
+  if (j == 0) {
+    Band b;
+    b.NL = 0;
+    b.NU = 0;
+    b.past_end = false;
+    if (live) b = mode == 0 ? band_limits(freqs[slot], tol, 2 * H, sr, bins) : band_limits(centre, slot > 2 ? tol / 2 : tol, 2 * H, sr, bins);
+    side[0] = b.NL;
+    side[1] = b.NU;
+    side[2] = b.past_end ? 1 : 0;
+  }
+  float2 v[8];
+  const long long base = (long long)fr * hop - (n_fft >> 1);
+  const bool interior = live && base >= 0 && base + n_fft <= (long long)n;
+  if (interior && n_fft == 2 * H) {
+    const float* xs = x + base * x_stride;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t0 = 2 * (j + q * T);
+      const float2 w = *reinterpret_cast<const float2*>(window + t0);
+      v[q] = make_float2(w.x * xs[(int64_t)t0 * x_stride], w.y * xs[(int64_t)(t0 + 1) * x_stride]);
+    }
+  } else if (interior) {
+    const float* xs = x + base * x_stride;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t0 = 2 * (j + q * T);
+      float2 z = make_float2(0.0f, 0.0f);
+      if (t0 + 1 < n_fft) {
+        const float2 w = *reinterpret_cast<const float2*>(window + t0);
+        z.x = w.x * xs[(int64_t)t0 * x_stride];
+        z.y = w.y * xs[(int64_t)(t0 + 1) * x_stride];
+      } else if (t0 < n_fft) {
+        z.x = window[t0] * xs[(int64_t)t0 * x_stride];
+      }
+      v[q] = z;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int t0 = 2 * (j + q * T);
+      float2 z = make_float2(0.0f, 0.0f);
+      if (live) {
+        if (t0 < n_fft) z.x = window[t0] * x[reflect_index(base + t0, n) * x_stride];
+        if (t0 + 1 < n_fft) z.y = window[t0 + 1] * x[reflect_index(base + t0 + 1, n) * x_stride];
+      }
+      v[q] = z;
+    }
+  }
+  float2 pw[P + 1];
+#pragma unroll
+  for (int i = 0; i < P; ++i) pw[i] = post[j + i * T];
+  pw[P] = post[H / 2];
+  fft_core<LOGH>(v, X, j, tw);
+  const float hs = 0.5f * scale;
+  constexpr bool kLinearPad = (T % 8) == 0;
+  constexpr int kPadStep = T + T / 8;
+  const int lp_k0 = lpad(j), lp_m0 = lpad(H - j);
+  // the float32 magnitudes of this lane's bins, in registers until every lane of the frame has read X
+  float mg[2 * P + 1];
+  auto keep = [&](int s, float re, float im) { mg[s] = fmaf(__builtin_amdgcn_sqrtf(fmaf(re, re, im * im)), hs, 1e-7f); };
+#pragma unroll
+  for (int i = 0; i <= P; ++i) {
+    const int k = (i < P) ? j + i * T : H / 2;
+    if (i == P && j != 0) break;
+    int sk = lpad(k), sm = lpad((H - k) & (H - 1));
+    if (kLinearPad && i < P) {
+      sk = lp_k0 + i * kPadStep;
+      sm = (i == 0 && j == 0) ? 0 : lp_m0 - i * kPadStep;
+    }
+    const float2 zk = X[sk];
+    const float2 zc = cconj(X[sm]);
+    const float2 ev = cadd(zk, zc);
+    const float2 t = cmul(pw[i], csub(zk, zc));
+    keep(2 * i, ev.x + t.y, ev.y - t.x);                     // bin k
+    if (i < P) keep(2 * i + 1, ev.x - t.y, -ev.y - t.x);     // bin H - k
+  }
+  frame_sync<T>();                                           // the untangle reads of X are done: the slot becomes the band's values
+  Band b;
+  b.NL = side[0];
+  b.NU = side[1];
+  b.past_end = side[2] != 0;
+  const bool has_band = live && b.NL >= 0 && b.NL < b.NU;    // uniform over the frame's lanes
+  float* D = reinterpret_cast<float*>(X);                    // D[k], k <= H: 2 FrameLds floats are there
+  if (has_band) {
+    const int lo = b.NL - 1, hi = b.NU < bins - 1 ? b.NU : bins - 1;
+    auto deposit = [&](int k, float m) {
+      if ((k >= lo && k <= hi) || (b.NL == 0 && k == bins - 1)) D[k] = db ? (float)(20.0 * log10_pos((double)m)) : m;
+    };
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      deposit(j + i * T, mg[2 * i]);
+      deposit(H - (j + i * T), mg[2 * i + 1]);
+    }
+    if (j == 0) deposit(H / 2, mg[2 * P]);
+  }
+  frame_sync<T>();
+  float best = -INFINITY;
+  int arg = 0x7fffffff;
+  if (has_band) {
+    for (int k = b.NL + j; k < b.NU; k += T) {
+      const float val = D[k];
+      if (val > best) {                                      // ascending bins per lane: strict > keeps the first occurrence
+        best = val;
+        arg = k;
+      }
+    }
+  }
+  constexpr int kLanes = T < kWave ? T : kWave;
+#pragma unroll
+  for (int o = kLanes / 2; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, kWave);
+    const int oa = __shfl_xor(arg, o, kWave);
+    if (ov > best || (ov == best && oa < arg)) {
+      best = ov;
+      arg = oa;
+    }
+  }
+  if constexpr (T > kWave) {
+    if ((j & (kWave - 1)) == 0) {
+      side[4 + 2 * (j / kWave)] = __float_as_int(best);
+      side[5 + 2 * (j / kWave)] = arg;
+    }
+    __syncthreads();
+    if (j == 0) {
+      for (int w = 1; w < kWaves; ++w) {
+        const float ov = __int_as_float(side[4 + 2 * w]);
+        const int oa = side[5 + 2 * w];
+        if (ov > best || (ov == best && oa < arg)) {
+          best = ov;
+          arg = oa;
+        }
+      }
+    }
+  }
+  if (j != 0 || !live) return;
+  if (!has_band) {
+    atomicOr(status, 1);
+    return;
+  }
+  if (arg == 0x7fffffff || D[b.NL] != D[b.NL]) arg = b.NL;   // nothing but NaN, or a NaN on the first bin: K_track's walk stays on NL
+  freqs[slot] = peak_refine([&](int k) { return D[k]; }, arg, b, bins, 2 * H, sr, status);
 }
 
 // ---- transforms above 8192 points: four-step FFT ----------------------------------------------------------
@@ -2268,6 +2445,78 @@ int par_stft_mean_db_f32(int device, const float* x, int64_t n, int64_t x_stride
   hipLaunchKernelGGL(k_mean_db_reduce, dim3((unsigned)ceil_div(bins, 256), (unsigned)n_ch), dim3(256), 0, s, part, n_runs, bins, n_frames, mean);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
+}
+
+// Peak / Peak Track straight from the samples (k_stft_peak): what par_track_peak_f64 traces on the mode-1 spectrogram of x
+// (db: on its float32 dB), without the spectrogram.
+int par_stft_track_peak_f64(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, int zeropad,
+                            const float* window, int64_t frame_0, int64_t count, double* freqs, double sr,
+                            double tolerance_oct, int mode, int db, int32_t* status, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(x && window && freqs && status, PAR_ERR_ARG, "par_stft_track_peak_f64: null pointer");
+  PAR_REQUIRE(n >= 1 && x_stride >= 1 && hop >= 1 && zeropad >= 1 && n_fft >= 2, PAR_ERR_ARG,
+              "par_stft_track_peak_f64: bad sizes (n %lld, stride %lld, n_fft %d, hop %d, zeropad %d)", (long long)n, (long long)x_stride,
+              n_fft, hop, zeropad);
+  PAR_REQUIRE(count >= 0 && frame_0 >= 0 && count <= par_stft_frames(n, n_fft, hop) && frame_0 <= par_stft_frames(n, n_fft, hop) - count,
+              PAR_ERR_ARG, "par_stft_track_peak_f64: frames [%lld, %lld + %lld) of %lld", (long long)frame_0, (long long)frame_0,
+              (long long)count, (long long)par_stft_frames(n, n_fft, hop));
+  PAR_REQUIRE((mode == 0 || mode == 1) && (db == 0 || db == 1), PAR_ERR_ARG, "par_stft_track_peak_f64: mode and db must be 0 or 1");
+  PAR_REQUIRE(stft_mean_supported(n_fft, zeropad), PAR_ERR_UNSUPPORTED,
+              "par_stft_track_peak_f64: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)n_fft * zeropad);
+  if (count == 0) return PAR_OK;
+  const int M = n_fft * zeropad, H = M / 2;
+  PAR_HIP_CHECK(hipSetDevice(device));
+  Twiddles tw;
+  int rc = get_twiddles(device, M, &tw);
+  if (rc != PAR_OK) return rc;
+  hipStream_t s = as_stream(stream);
+  PAR_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+  double centre = 0.0;
+  if (mode == 1) {                                           // the band of every frame sits on the first trail frequency
+    PAR_HIP_CHECK(hipMemcpyAsync(&centre, freqs, sizeof(double), hipMemcpyDeviceToHost, s));
+    PAR_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  const float scale = (float)(1.0 / sqrt((double)n_fft));
+  // the frames, then per frame 4 ints of band and one (value, bin) pair per wave of the frame
+#define PAR_PEAK_LDS(LH)                                                     \
+  ((size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2) +    \
+   (size_t)FftGeom<LH>::Frames * (4 + 2 * (FftGeom<LH>::T > kWave ? FftGeom<LH>::T / kWave : 1)) * sizeof(int))
+#define PAR_PEAK_LAUNCH_U(LH, UN)                                                                                              \
+  hipLaunchKernelGGL((k_stft_peak<LH, UN>), dim3((unsigned)(ceil_div(ceil_div(count, FftGeom<LH>::Frames), 8) * 8)),            \
+                     dim3(FftGeom<LH>::Threads), PAR_PEAK_LDS(LH), s, x, n, x_stride, n_fft, hop, window, tw.w, tw.post, frame_0, \
+                     count, freqs, centre, sr, tolerance_oct, mode, db, status, scale)
+#define PAR_PEAK_LAUNCH(LH)                         \
+  do {                                              \
+    if (x_stride == 1) PAR_PEAK_LAUNCH_U(LH, true); \
+    else PAR_PEAK_LAUNCH_U(LH, false);              \
+  } while (0)
+  switch (ilog2(H)) {
+    case 3: PAR_PEAK_LAUNCH(3); break;
+    case 4: PAR_PEAK_LAUNCH(4); break;
+    case 5: PAR_PEAK_LAUNCH(5); break;
+    case 6: PAR_PEAK_LAUNCH(6); break;
+    case 7: PAR_PEAK_LAUNCH(7); break;
+    case 8: PAR_PEAK_LAUNCH(8); break;
+    case 9: PAR_PEAK_LAUNCH(9); break;
+    case 10: PAR_PEAK_LAUNCH(10); break;
+    case 11: PAR_PEAK_LAUNCH(11); break;
+    case 12: PAR_PEAK_LAUNCH(12); break;
+    case 13: {
+      // 72 KB of LDS, above a kernel's default 64 KB (as k_stft at this size)
+      for (const void* fn : {reinterpret_cast<const void*>(&k_stft_peak<13, true>), reinterpret_cast<const void*>(&k_stft_peak<13, false>)}) {
+        const int rc2 = raise_dynamic_lds(fn, (int)PAR_PEAK_LDS(13), device);
+        if (rc2 != PAR_OK) return rc2;
+      }
+      PAR_PEAK_LAUNCH(13);
+      break;
+    }
+    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_track_peak_f64: unsupported size");
+  }
+#undef PAR_PEAK_LAUNCH
+#undef PAR_PEAK_LAUNCH_U
+#undef PAR_PEAK_LDS
+  PAR_HIP_CHECK(hipGetLastError());
+  return check_empty(status, s, "par_stft_track_peak_f64");
 }
 
 // Frames of more than 8192 points (up to 2^21): four-step transform through a caller-owned scratch of

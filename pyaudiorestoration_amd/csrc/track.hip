@@ -6,74 +6,12 @@
 // (util/correlation.py:42-46).  The spectrogram is FRAME-MAJOR float32 (what K_stft writes), so a
 // frame's band is a contiguous run.  Band/bin arithmetic is float64 like the reference.
 #include "par_common.h"
+#include "track_band.h"
 #include <math.h>
 #include <mutex>
 #include <set>
 
 namespace par {
-
-struct Band {
-  int NL, NU;
-  bool past_end;       // NU reached past the last bin before the clip (a numpy slice clips silently; a product with a
-                       // full-length window does not)
-};
-
-__device__ __forceinline__ int freq_to_bin(double f, int fft_size, double sr, int bins) {
-  long long b = llrint(f * (double)fft_size / sr);        // Python round(): half-to-even
-  if (b > bins - 1) b = bins - 1;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-__device__ __forceinline__ Band band_limits(double freq, double tol, int fft_size, double sr, int bins) {
-  const double lf = log2(freq);
-  double fL = exp2(lf - tol), fU = exp2(lf + tol);
-  fL = fL > 1.0 ? fL : 1.0;                                // max(1.0, fL)
-  fU = fU < sr / 2 ? fU : sr / 2;                          // min(sr/2, fU)
-  Band b;
-  b.NL = freq_to_bin(fL, fft_size, sr, bins);
-  b.NU = freq_to_bin(fU, fft_size, sr, bins);
-  while (b.NU - b.NL < 4) {                                // min_bins = 4
-    b.NL -= 1;
-    b.NU += 1;
-  }
-  // A band widened below bin 0 (both edges on bin 1: a frequency below the transform's resolution) is an EMPTY
-  // numpy slice [-k:NU] in the reference, whose argmax raises; reported through `empty`, never silently clamped.
-  b.past_end = b.NU > bins;
-  if (b.NU > bins) b.NU = bins;
-  return b;
-}
-
-// status bits: 1 empty band (ValueError), 2 peak on the last bin: is_peak() reads fft_frame[peak_i + 1] (IndexError),
-// 4 band widened past the last bin: window(NU - NL) * spectrum[NL:NU] does not broadcast (ValueError); freq_2_bin caps
-// both edges at bins - 1 and min_bins is 4, so such a slice always keeps >= 3 bins against a window of >= 4
-__device__ __forceinline__ double peak_freq(const float* __restrict__ col, Band b, int bins, int fft_size, double sr,
-                                            int* __restrict__ status) {
-  int arg = b.NL;
-  float best = col[b.NL];
-  for (int k = b.NL + 1; k < b.NU; ++k) {
-    const float v = col[k];
-    if (v > best) {                                        // first occurrence of the maximum (np.argmax)
-      best = v;
-      arg = k;
-    }
-  }
-  double x = (double)arg;
-  if (b.past_end) {
-    atomicOr(status, 4);
-    return x / (double)fft_size * sr;
-  }
-  if (arg == bins - 1) {
-    atomicOr(status, 2);
-    return x / (double)fft_size * sr;
-  }
-  const double fm = (double)col[(arg - 1 + bins) % bins], f0 = (double)col[arg], fp = (double)col[arg + 1];
-  if (fm < f0 && f0 > fp) {
-    // parabolic(): xv = 1/2*(f[x-1]-f[x+1]) / (f[x-1]-2f[x]+f[x+1]) + x
-    x = 0.5 * (fm - fp) / (fm - 2.0 * f0 + fp) + x;
-  }
-  return x / (double)fft_size * sr;
-}
 
 __device__ __forceinline__ bool empty_band(const Band& b, int* __restrict__ empty) {
   if (b.NL >= 0 && b.NL < b.NU) return false;
@@ -519,6 +457,64 @@ __global__ __launch_bounds__(256) void k_piptrack(const float* __restrict__ mag,
   }
 }
 
+// ---- cyclic fold (experiments/cyclic_wow.py:9-27 get_avg, :50-59 the search loop) ---------------------------------------------
+// For the candidate cycle length P = p_first + blockIdx.x the track is cut into V = count / P whole views of P frames and
+// averaged over the views: np.mean(np.split(v[:V * P], V), axis=0).  numpy reduces the outer axis of a C-contiguous array row
+// after row, so a phase's sum is v[p] + v[P + p] + ... in view order from view 0, then one division by V; that order is kept
+// here and the result equals numpy's bit for bit for P >= 2 (at P == 1 numpy sees one contiguous run and sums it pairwise; the
+// order here stays the stated one).  One workgroup per candidate, its lanes over the phase (adjacent lanes read
+// adjacent addresses in every view); the candidate's max and min of the averages meet through LDS, NaN propagating as np.max /
+// np.min propagate it.  No atomics.
+__global__ __launch_bounds__(256) void k_cycle_fold(const double* __restrict__ v, int64_t count, int p_first, double* __restrict__ avg,
+                                                    int64_t avg_pitch, double* __restrict__ delta) {
+  __shared__ double red_hi[4], red_lo[4];
+  __shared__ int red_nan[4];
+  const int c = blockIdx.x;
+  const int64_t P = (int64_t)p_first + c;
+  const int64_t V = count / P;
+  double hi = -INFINITY, lo = INFINITY;
+  int has_nan = 0;
+  for (int64_t p = threadIdx.x; p < P; p += blockDim.x) {
+    const double* col = v + p;
+    double s = col[0];
+    int64_t w = 1;
+    for (; w + 4 <= V; w += 4) {                             // four loads in flight, the additions in view order
+      const double a0 = col[w * P], a1 = col[(w + 1) * P], a2 = col[(w + 2) * P], a3 = col[(w + 3) * P];
+      s += a0;
+      s += a1;
+      s += a2;
+      s += a3;
+    }
+    for (; w < V; ++w) s += col[w * P];
+    const double a = s / (double)V;
+    if (avg) avg[(int64_t)c * avg_pitch + p] = a;
+    if (a != a) has_nan = 1;
+    hi = a > hi ? a : hi;
+    lo = a < lo ? a : lo;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double oh = __shfl_xor(hi, o, kWave), ol = __shfl_xor(lo, o, kWave);
+    hi = oh > hi ? oh : hi;
+    lo = ol < lo ? ol : lo;
+    has_nan |= __shfl_xor(has_nan, o, kWave);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    red_hi[threadIdx.x / kWave] = hi;
+    red_lo[threadIdx.x / kWave] = lo;
+    red_nan[threadIdx.x / kWave] = has_nan;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < (int)(blockDim.x / kWave); ++w) {
+      hi = red_hi[w] > hi ? red_hi[w] : hi;
+      lo = red_lo[w] < lo ? red_lo[w] : lo;
+      has_nan |= red_nan[w];
+    }
+    delta[c] = has_nan ? (double)NAN : hi - lo;
+  }
+}
+
 }  // namespace par
 
 extern "C" {
@@ -548,20 +544,6 @@ int par_zero_crossings_f64(int device, const double* x, int64_t n, int64_t* work
   if (total == 0) return PAR_OK;
   hipLaunchKernelGGL(k_zc_write, dim3((unsigned)n_tiles), dim3(256), 0, s, x, n, offs, reinterpret_cast<long long*>(idx));
   PAR_HIP_CHECK(hipGetLastError());
-  return PAR_OK;
-}
-
-// Shared tail: read the "empty band" flag back (one 4-byte copy; the callers need the traced freqs on the host anyway).
-static int check_empty(int* d_flag, hipStream_t s, const char* who) {
-  int h = 0;
-  PAR_HIP_CHECK(hipMemcpyAsync(&h, d_flag, sizeof(h), hipMemcpyDeviceToHost, s));
-  PAR_HIP_CHECK(hipStreamSynchronize(s));
-  PAR_REQUIRE(!(h & 1), PAR_ERR_EMPTY_BAND,
-              "%s: a tracking band is empty (frequency below the transform's resolution: the reference's slice "
-              "[NL:NU] with NL < 0 is empty and its argmax raises)", who);
-  PAR_REQUIRE(!(h & 2), PAR_ERR_INDEX, "%s: the peak sits on the last bin (is_peak() reads fft_frame[peak_i + 1]: IndexError)", who);
-  PAR_REQUIRE(!(h & 4), PAR_ERR_SHAPE, "%s: the band reaches past the last bin (operands could not be broadcast together: "
-              "np.hanning(NU - NL) against the clipped slice)", who);
   return PAR_OK;
 }
 
@@ -716,6 +698,25 @@ int par_piptrack_f32(int device, const float* mag, int64_t n_frames, int bins, i
   hipLaunchKernelGGL(k_piptrack, dim3((unsigned)ceil_div(n_frames, 4)), dim3(256), 0, as_stream(stream), mag, bins,
                      mag_pitch ? mag_pitch : (int64_t)bins, n_frames, scale,
                      offset, fft_size, sr, fmin, fmax, threshold, pitches, mags);
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+// Cyclic fold of a track at n_cand candidate cycle lengths from p_first on (k_cycle_fold): avg[c][0 .. P) and delta[c] =
+// max - min of that row.  Does not synchronise.
+int par_cycle_fold_f64(int device, const double* v, int64_t count, int p_first, int n_cand, double* avg, int64_t avg_pitch,
+                       double* delta, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(v && delta, PAR_ERR_ARG, "par_cycle_fold_f64: null pointer");
+  PAR_REQUIRE(p_first >= 1 && n_cand >= 1 && count >= 0, PAR_ERR_ARG, "par_cycle_fold_f64: bad sizes (p_first=%d n_cand=%d count=%lld)",
+              p_first, n_cand, (long long)count);
+  PAR_REQUIRE((int64_t)p_first + n_cand - 1 <= count, PAR_ERR_ARG,
+              "par_cycle_fold_f64: cycle length %lld is longer than the track of %lld frames (the reference's np.split into 0 sections raises)",
+              (long long)p_first + n_cand - 1, (long long)count);
+  PAR_REQUIRE(!avg || avg_pitch >= (int64_t)p_first + n_cand - 1, PAR_ERR_ARG, "par_cycle_fold_f64: avg_pitch %lld < the longest cycle %lld",
+              (long long)avg_pitch, (long long)p_first + n_cand - 1);
+  PAR_HIP_CHECK(hipSetDevice(device));
+  hipLaunchKernelGGL(k_cycle_fold, dim3((unsigned)n_cand), dim3(256), 0, as_stream(stream), v, count, p_first, avg, avg_pitch, delta);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }
