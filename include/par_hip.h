@@ -475,6 +475,12 @@ int par_sosfiltfilt_batch_f64(int device, const double* sos, const double* zi, i
                               int64_t x_stride, int n_sig, int64_t n, int64_t padlen, double* work, int64_t work_len, double* y,
                               int64_t y_stride, void* stream);
 
+/* The block matrices both forms chain their 256-sample blocks with, for one section (HOST only, no device call; added at
+ * ABI 109: par_version() stays 109).  section6 HOST f64[6] = (b0, b1, b2, a0, a1, a2); P4, Q4 HOST f64[4], row-major:
+ * P = A^256, Q = A^65536 with A = [[-a1, 1], [-a2, 0]], each the exact power rounded to double (formed in double-double;
+ * measured within one ulp of the largest entry, NOTES.md).  Exported so that the tests can pin them to the exact integer power. */
+void par_sosfilt_block_matrices(const double* section6, double* P4, double* Q4);
+
 /* ---- Spectral Expander (expander_gui.py) and time-averaged spectra (util/spectrum_flat.py), ABI 107 ------------------------ */
 /* Band dB straight out of the STFT: out[f] (DEVICE f64[par_stft_frames(n, n_fft, hop)]) = mean over b in [bin_l, bin_u) of
  * 20 log10(|X_f[b]| / sqrt(n_fft) + 1e-7), the magnitude being the float32 value par_stft_f32 mode 1 writes and the log and

@@ -42,6 +42,8 @@ def lib():
         L.oracle_synth_signal.argtypes = [vp, i64, i64, dbl, ctypes.c_uint64]
         L.oracle_synth_curve.restype = None
         L.oracle_synth_curve.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl]
+        L.oracle_sosfiltfilt_ld.restype = ci
+        L.oracle_sosfiltfilt_ld.argtypes = [vp, ci, vp, i64, i64, vp]
         _lib = L
     return _lib
 
@@ -109,6 +111,19 @@ def stft(x, n_fft, hop, window, zeropad=1, mode=0, threads=1):
     if mode == 0:
         return out.view(np.complex64).T
     return out.T
+
+
+def sosfiltfilt_ld(sos, x, padlen):
+    """scipy.signal.sosfiltfilt(sos, x, padlen=padlen) carried in long double from the odd extension to the trim (par_oracle.c)"""
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if sos.ndim != 2 or sos.shape[1] != 6 or x.ndim != 1:
+        raise ValueError("sos must be (n_sections, 6) and x one-dimensional")
+    y = np.empty(len(x), dtype=np.float64)
+    rc = lib().oracle_sosfiltfilt_ld(_p(sos), sos.shape[0], _p(x), len(x), int(padlen), _p(y))
+    if rc != 0:
+        raise ValueError(f"oracle_sosfiltfilt_ld status {rc}")
+    return y
 
 
 def synth_signal(start, count, sr, seed=0x5EED):

@@ -14,6 +14,7 @@
  *   oracle_sinc_mt        util/resampling.py:30-46    sinc_wrapper_mt: one contiguous chunk per thread
  *   oracle_stft(_mt)      util/fourier.py:23-29, 37-82, 136-166  stft / get_mag via the numpy framing (frames over threads)
  *   oracle_synth_*        SURVEY 8d closed-form workload (same as tests/inputs.py)
+ *   oracle_sosfiltfilt_ld util/filters.py:24  scipy.signal.sosfiltfilt in long double (pinned to scipy, not to a golden vector)
  * Build: gcc -O2 -fPIC -shared -pthread par_oracle.c -lm   (no -ffast-math: numpy order is kept)
  */
 #include <math.h>
@@ -454,4 +455,50 @@ void oracle_synth_curve(double* st, double* sp, int64_t m, double dur, double sr
     st[i] = t * sr;
     sp[i] = 1.0 + depth * sin(2.0 * M_PI * rate * t + phase);
   }
+}
+
+/* ------------------------------------------------------------------ sosfiltfilt in long double */
+/* scipy.signal.sosfiltfilt(sos, x, padtype='odd', padlen=padlen) with every value held in long double (x87 80-bit: 64-bit
+ * significand): the odd extension, sosfilt_zi in closed form (the state a unit step settles in: z0 = g - b0, z1 = b2 - a2 g with
+ * the section's DC gain g = (b0 + b1 + b2) / (1 + a1 + a2), scaled by the gain of the sections before it), the forward and the
+ * backward cascade with the transposed direct-form-II biquad, the trim.  Nothing is rounded to double before y is written, so
+ * against this scipy's own float64 run shows its rounding error and a float64 kernel shows its own.
+ *   sos [n_sections][6] (a0 is divided out), x [n], y [n]; returns 0, or -1 for n <= padlen, a bad count or no memory. */
+int oracle_sosfiltfilt_ld(const double* sos, int n_sections, const double* x, int64_t n, int64_t padlen, double* y) {
+  if (n_sections < 1 || n_sections > 64 || padlen < 0 || n <= padlen) return -1;
+  const int64_t L = n + 2 * padlen;
+  long double* e = (long double*)malloc(sizeof(long double) * (size_t)L);
+  if (!e) return -1;
+  long double b0[64], b1[64], b2[64], a1[64], a2[64], zi0[64], zi1[64], z0[64], z1[64];
+  long double scale = 1.0L;
+  for (int s = 0; s < n_sections; ++s) {
+    const double* c = sos + 6 * s;
+    const long double a0 = c[3];
+    b0[s] = c[0] / a0; b1[s] = c[1] / a0; b2[s] = c[2] / a0; a1[s] = c[4] / a0; a2[s] = c[5] / a0;
+    const long double g = (b0[s] + b1[s] + b2[s]) / (1.0L + a1[s] + a2[s]);
+    zi0[s] = scale * (g - b0[s]);
+    zi1[s] = scale * (b2[s] - a2[s] * g);
+    scale *= g;
+  }
+  for (int64_t i = 0; i < padlen; ++i) e[i] = 2.0L * x[0] - (long double)x[padlen - i];
+  for (int64_t i = 0; i < n; ++i) e[padlen + i] = x[i];
+  for (int64_t i = 0; i < padlen; ++i) e[padlen + n + i] = 2.0L * x[n - 1] - (long double)x[n - 2 - i];
+  for (int dir = 0; dir < 2; ++dir) {
+    const long double first = dir ? e[L - 1] : e[0];
+    for (int s = 0; s < n_sections; ++s) { z0[s] = zi0[s] * first; z1[s] = zi1[s] * first; }
+    for (int64_t k = 0; k < L; ++k) {
+      const int64_t i = dir ? L - 1 - k : k;
+      long double v = e[i];
+      for (int s = 0; s < n_sections; ++s) {
+        const long double w = b0[s] * v + z0[s];
+        z0[s] = b1[s] * v - a1[s] * w + z1[s];
+        z1[s] = b2[s] * v - a2[s] * w;
+        v = w;
+      }
+      e[i] = v;
+    }
+  }
+  for (int64_t i = 0; i < n; ++i) y[i] = (double)e[padlen + i];
+  free(e);
+  return 0;
 }

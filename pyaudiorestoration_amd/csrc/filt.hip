@@ -10,10 +10,18 @@
 // An IIR is a serial recurrence, but a LINEAR one: state' = A*state + B*x.  So the signal is cut into
 // blocks of kFiltBlock samples; every block (one lane each) computes its zero-state end state in
 // parallel, a tiny serial pass chains  s[b+1] = A^blk * s[b] + r[b]  over the blocks, and every block
-// is then re-run from its true initial state writing the outputs.  Results equal scipy's up to
-// floating-point re-association of the state propagation (~1e-15 relative).
+// is then re-run from its true initial state writing the outputs.
+//
+// Accuracy is stated against a run of the same recurrence in 80-bit long double, next to scipy's own float64 run: with
+// e = max |y - that run| / max |that run|, e_gpu <= 5 e_scipy on every cascade, signal and length of tests/filt_inputs.py
+// (measured on the MI355X, NOTES.md "K_sosfiltfilt against a long-double ..."; test_filt_kernels_gpu.py asserts 3 x that).
+// On wide bands both are ~1e-14; on the narrow bands of the wow and lag tools (2 Hz low-pass at 44.1 kHz: e_scipy 2e-10,
+// 1-2 Hz band-pass: 1e-9 .. 4e-8) the recurrence itself is that ill-conditioned and the kernels follow it, no worse.  That
+// takes P and Q as exact powers (block_matrices) and a chain step summed with its rounding errors (chain_row); with P and Q
+// squared in plain double and plain sums the same bands sat at 1e-7 .. 1e-5, up to 10^5 x scipy.
 #include "par_common.h"
 #include <math.h>
+#include <algorithm>
 #include <vector>
 
 namespace par {
@@ -129,19 +137,40 @@ __global__ void k_sos_block_zero_direct(const double* __restrict__ u, int64_t L,
   r[2 * b + 1] = z1;
 }
 
-// serial chain over block boundaries: s[b+1] = P * s[b] + r[b],  P = A^kFiltBlock (host-computed)
-__global__ void k_sos_chain(const double* __restrict__ r, int64_t nblk, double p00, double p01, double p10, double p11,
-                            double zi0, double zi1, const double* __restrict__ scale_sample, double* __restrict__ s) {
+// ---- the chain over the block boundaries:  s[b+1] = P s[b] + r[b],  P = A^kFiltBlock (host: block_matrices below) ----------------
+// On a narrow band near z = 1 the entries of P are ~250 and cancel in P s (the state is nearly (y, -y)), so one plain step rounds
+// at 250 ulp of the state where the recurrence itself rounds at one ulp per sample: measured on the MI355X with exact P and Q,
+// 25 .. 83 times scipy's own error on the 2 Hz low-pass and the 1-2 Hz / 50-60 Hz band-passes (NOTES.md).  A step is therefore
+// summed with its rounding errors: P comes as head + tail (the two halves of the host's double-double power), both products
+// and both sums are error-free transformations, and the row is rounded once.  The state stays one double per component -- that
+// rounding is no larger than the one every sample of the recurrence makes.  With this the whole filter sits at 1 .. 5 x scipy.
+struct BlockMat {                      // row-major heads and tails
+  double h00, h01, h10, h11, l00, l01, l10, l11;
+};
+__device__ __forceinline__ double chain_row(double ph0, double pl0, double ph1, double pl1, double z0, double z1, double r) {
+#pragma clang fp contract(off)         // a + b must stay fl(a + b), not fma(ph0, z0, b)
+  const double a = ph0 * z0, ae = __builtin_fma(ph0, z0, -a);
+  const double b = ph1 * z1, be = __builtin_fma(ph1, z1, -b);
+  const double s = a + b, bb = s - a, se = (a - (s - bb)) + (b - bb);
+  const double t = s + r, rr = t - s, te = (s - (t - rr)) + (r - rr);
+  return t + (((ae + be) + (pl0 * z0 + pl1 * z1)) + (se + te));
+}
+__device__ __forceinline__ void chain_step(const BlockMat& m, double& z0, double& z1, double r0, double r1) {
+  const double n0 = chain_row(m.h00, m.l00, m.h01, m.l01, z0, z1, r0);
+  const double n1 = chain_row(m.h10, m.l10, m.h11, m.l11, z0, z1, r1);
+  z0 = n0;
+  z1 = n1;
+}
+
+__global__ void k_sos_chain(const double* __restrict__ r, int64_t nblk, BlockMat m, double zi0, double zi1,
+                            const double* __restrict__ scale_sample, double* __restrict__ s) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const double sc = *scale_sample;
   double z0 = zi0 * sc, z1 = zi1 * sc;
   for (int64_t b = 0; b < nblk; ++b) {
     s[2 * b] = z0;
     s[2 * b + 1] = z1;
-    const double n0 = p00 * z0 + p01 * z1 + r[2 * b];
-    const double n1 = p10 * z0 + p11 * z1 + r[2 * b + 1];
-    z0 = n0;
-    z1 = n1;
+    chain_step(m, z0, z1, r[2 * b], r[2 * b + 1]);
   }
 }
 
@@ -151,23 +180,17 @@ __global__ void k_sos_chain(const double* __restrict__ r, int64_t nblk, double p
 // (k_sos_chain on the super-block records), and every super-block then re-walks its own blocks from its true state
 // (k_sos_super_run).  Same affine maps, composed in a different order: float64 re-association only.
 constexpr int kFiltSuper = 256;
-__global__ void k_sos_super_zero(const double* __restrict__ r, int64_t nblk, double p00, double p01, double p10, double p11,
-                                 int64_t nsup, double* __restrict__ R) {
+__global__ void k_sos_super_zero(const double* __restrict__ r, int64_t nblk, BlockMat m, int64_t nsup, double* __restrict__ R) {
   const int64_t B = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (B >= nsup) return;
   const int64_t b0 = B * kFiltSuper, b1 = b0 + kFiltSuper < nblk ? b0 + kFiltSuper : nblk;
   double z0 = 0.0, z1 = 0.0;
-  for (int64_t b = b0; b < b1; ++b) {
-    const double n0 = p00 * z0 + p01 * z1 + r[2 * b];
-    const double n1 = p10 * z0 + p11 * z1 + r[2 * b + 1];
-    z0 = n0;
-    z1 = n1;
-  }
+  for (int64_t b = b0; b < b1; ++b) chain_step(m, z0, z1, r[2 * b], r[2 * b + 1]);
   R[2 * B] = z0;
   R[2 * B + 1] = z1;
 }
-__global__ void k_sos_super_run(const double* __restrict__ r, int64_t nblk, double p00, double p01, double p10, double p11,
-                                int64_t nsup, const double* __restrict__ S, double* __restrict__ s) {
+__global__ void k_sos_super_run(const double* __restrict__ r, int64_t nblk, BlockMat m, int64_t nsup,
+                                const double* __restrict__ S, double* __restrict__ s) {
   const int64_t B = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (B >= nsup) return;
   const int64_t b0 = B * kFiltSuper, b1 = b0 + kFiltSuper < nblk ? b0 + kFiltSuper : nblk;
@@ -175,10 +198,7 @@ __global__ void k_sos_super_run(const double* __restrict__ r, int64_t nblk, doub
   for (int64_t b = b0; b < b1; ++b) {
     s[2 * b] = z0;
     s[2 * b + 1] = z1;
-    const double n0 = p00 * z0 + p01 * z1 + r[2 * b];
-    const double n1 = p10 * z0 + p11 * z1 + r[2 * b + 1];
-    z0 = n0;
-    z1 = n1;
+    chain_step(m, z0, z1, r[2 * b], r[2 * b + 1]);
   }
 }
 
@@ -219,11 +239,11 @@ __global__ void k_copy_mid(const double* __restrict__ src, int64_t pad, int64_t 
 // (0.25 ms for 10^6 samples, of which the GPU is busy a few per cent).  Here the batch is the grid's y dimension.
 struct FiltParam {                       // one (signal, section): coefficients, P = A^kFiltBlock, Q = P^kFiltSuper, zi
   double b0, b1, b2, a1, a2;
-  double p00, p01, p10, p11;
-  double q00, q01, q10, q11;
+  BlockMat P, Q;
   double zi0, zi1, pad;
 };
-static_assert(sizeof(FiltParam) == 128, "FiltParam is uploaded as 16 doubles");
+constexpr int kFiltParamDoubles = 24;
+static_assert(sizeof(FiltParam) == 8 * kFiltParamDoubles, "FiltParam is uploaded as 24 doubles");
 
 __global__ void k_odd_ext_b(const double* __restrict__ x, int64_t x_stride, int64_t n, int64_t pad, double* __restrict__ ext) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -296,12 +316,7 @@ __global__ void k_sos_super_zero_b(const double* __restrict__ r, int64_t nblk, c
   const double* rs = r + 2 * (int64_t)sg * nblk;
   const int64_t b0 = B * kFiltSuper, b1 = b0 + kFiltSuper < nblk ? b0 + kFiltSuper : nblk;
   double z0 = 0.0, z1 = 0.0;
-  for (int64_t b = b0; b < b1; ++b) {
-    const double n0 = q.p00 * z0 + q.p01 * z1 + rs[2 * b];
-    const double n1 = q.p10 * z0 + q.p11 * z1 + rs[2 * b + 1];
-    z0 = n0;
-    z1 = n1;
-  }
+  for (int64_t b = b0; b < b1; ++b) chain_step(q.P, z0, z1, rs[2 * b], rs[2 * b + 1]);
   R[2 * ((int64_t)sg * nsup + B)] = z0;
   R[2 * ((int64_t)sg * nsup + B) + 1] = z1;
 }
@@ -316,10 +331,7 @@ __global__ void k_sos_chain_b(const double* __restrict__ R, int64_t nsup, const 
   for (int64_t B = 0; B < nsup; ++B) {
     S[2 * ((int64_t)sg * nsup + B)] = z0;
     S[2 * ((int64_t)sg * nsup + B) + 1] = z1;
-    const double n0 = q.q00 * z0 + q.q01 * z1 + R[2 * ((int64_t)sg * nsup + B)];
-    const double n1 = q.q10 * z0 + q.q11 * z1 + R[2 * ((int64_t)sg * nsup + B) + 1];
-    z0 = n0;
-    z1 = n1;
+    chain_step(q.Q, z0, z1, R[2 * ((int64_t)sg * nsup + B)], R[2 * ((int64_t)sg * nsup + B) + 1]);
   }
 }
 __global__ void k_sos_super_run_b(const double* __restrict__ r, int64_t nblk, const FiltParam* __restrict__ fp, int fp_stride,
@@ -335,10 +347,7 @@ __global__ void k_sos_super_run_b(const double* __restrict__ r, int64_t nblk, co
   for (int64_t b = b0; b < b1; ++b) {
     ss[2 * b] = z0;
     ss[2 * b + 1] = z1;
-    const double n0 = q.p00 * z0 + q.p01 * z1 + rs[2 * b];
-    const double n1 = q.p10 * z0 + q.p11 * z1 + rs[2 * b + 1];
-    z0 = n0;
-    z1 = n1;
+    chain_step(q.P, z0, z1, rs[2 * b], rs[2 * b + 1]);
   }
 }
 __global__ void k_sos_block_run_b(const double* __restrict__ u, int64_t L, int reverse, const FiltParam* __restrict__ fp,
@@ -367,19 +376,64 @@ __global__ void k_copy_mid_b(const double* __restrict__ src, int64_t L, int64_t 
   if (i < n) dst[(int64_t)blockIdx.y * y_stride + i] = src[(int64_t)blockIdx.y * L + i + pad];
 }
 
-static void mat_pow(double a00, double a01, double a10, double a11, int e, double* out) {
-  double p00 = 1, p01 = 0, p10 = 0, p11 = 1;
-  for (; e > 0; e >>= 1) {
-    if (e & 1) {
-      const double t00 = p00 * a00 + p01 * a10, t01 = p00 * a01 + p01 * a11;
-      const double t10 = p10 * a00 + p11 * a10, t11 = p10 * a01 + p11 * a11;
-      p00 = t00; p01 = t01; p10 = t10; p11 = t11;
-    }
-    const double s00 = a00 * a00 + a01 * a10, s01 = a00 * a01 + a01 * a11;
-    const double s10 = a10 * a00 + a11 * a10, s11 = a10 * a01 + a11 * a11;
-    a00 = s00; a01 = s01; a10 = s10; a11 = s11;
+// ---- block matrices (host) ----------------------------------------------------------------------------------------------------
+// P = A^kFiltBlock and Q = A^(kFiltBlock * kFiltSuper), A = [[-a1, 1], [-a2, 0]].  On the narrow bands of the wow and lag tools
+// (a1 ~ -2, a2 ~ 1) A is nearly defective: the entries of P are ~250 and cancel, and eight squarings in plain double left P with
+// 1e-11 of its largest entry in error, Q with up to 1e-4 -- times the length of the chain in the output (NOTES.md,
+// "K_sosfiltfilt against a long-double ...").  Both are therefore squared in double-double (two doubles per entry, ~106 bits)
+// and rounded once at the end; against the exact integer power that is within one ulp of the largest entry on every cascade measured.
+// Running the section's own recurrence from the two unit states was the alternative: it measures 1.6e-13 in P and 6e-10 in Q,
+// because each of its 65536 steps rounds; squaring in x87 long double 7e-15 and 7e-8.
+struct DD {
+  double hi, lo;
+};
+// (contraction is switched off in each: a fused multiply-add in these sums would break the error-free transformations)
+static inline DD dd_quick(double a, double b) {        // |a| >= |b|
+#pragma clang fp contract(off)
+  const double s = a + b;
+  return DD{s, b - (s - a)};
+}
+static inline DD dd_two_sum(double a, double b) {
+#pragma clang fp contract(off)
+  const double s = a + b, bb = s - a;
+  return DD{s, (a - (s - bb)) + (b - bb)};
+}
+static inline DD dd_add(DD x, DD y) {
+#pragma clang fp contract(off)
+  DD s = dd_two_sum(x.hi, y.hi);
+  const DD t = dd_two_sum(x.lo, y.lo);
+  s = dd_quick(s.hi, s.lo + t.hi);
+  return dd_quick(s.hi, s.lo + t.lo);
+}
+// Dekker's product with Veltkamp's split: exact without a hardware FMA (the host build has none by default)
+static inline DD dd_two_prod(double a, double b) {
+#pragma clang fp contract(off)
+  const double ta = 134217729.0 * a, tb = 134217729.0 * b;
+  const double ah = ta - (ta - a), bh = tb - (tb - b), al = a - ah, bl = b - bh;
+  const double p = a * b;
+  return DD{p, ((ah * bh - p) + ah * bl + al * bh) + al * bl};
+}
+static inline DD dd_mul(DD x, DD y) {
+#pragma clang fp contract(off)
+  const DD p = dd_two_prod(x.hi, y.hi);
+  return dd_quick(p.hi, p.lo + (x.hi * y.lo + x.lo * y.hi));
+}
+// m <- m * m, `times` times
+static void dd_mat_square(DD m[4], int times) {
+  for (int i = 0; i < times; ++i) {
+    const DD bc = dd_mul(m[1], m[2]), tr = dd_add(m[0], m[3]);
+    const DD n00 = dd_add(dd_mul(m[0], m[0]), bc), n11 = dd_add(dd_mul(m[3], m[3]), bc);
+    const DD n01 = dd_mul(m[1], tr), n10 = dd_mul(m[2], tr);
+    m[0] = n00; m[1] = n01; m[2] = n10; m[3] = n11;
   }
-  out[0] = p00; out[1] = p01; out[2] = p10; out[3] = p11;
+}
+static_assert(kFiltBlock == 256 && kFiltSuper == 256, "block_matrices squares eight times per level");
+static void block_matrices(double a1, double a2, BlockMat& P, BlockMat& Q) {
+  DD m[4] = {{-a1, 0.0}, {1.0, 0.0}, {-a2, 0.0}, {0.0, 0.0}};
+  dd_mat_square(m, 8);
+  P = BlockMat{m[0].hi, m[1].hi, m[2].hi, m[3].hi, m[0].lo, m[1].lo, m[2].lo, m[3].lo};
+  dd_mat_square(m, 8);
+  Q = BlockMat{m[0].hi, m[1].hi, m[2].hi, m[3].hi, m[0].lo, m[1].lo, m[2].lo, m[3].lo};
 }
 
 }  // namespace par
@@ -393,6 +447,13 @@ int64_t par_sosfiltfilt_work_len(int64_t n, int64_t padlen) {
   return 2 * L + 4 * nblk + 4 * nsup + 8;
 }
 
+void par_sosfilt_block_matrices(const double* section6, double* P4, double* Q4) {
+  par::BlockMat P, Q;
+  par::block_matrices(section6[4], section6[5], P, Q);
+  P4[0] = P.h00; P4[1] = P.h01; P4[2] = P.h10; P4[3] = P.h11;
+  Q4[0] = Q.h00; Q4[1] = Q.h01; Q4[2] = Q.h10; Q4[3] = Q.h11;
+}
+
 int par_sosfiltfilt_f64(int device, const double* sos, const double* zi, int n_sections, const double* x, int64_t n,
                         int64_t padlen, double* work, int64_t work_len, double* y, void* stream) {
   using namespace par;
@@ -402,6 +463,8 @@ int par_sosfiltfilt_f64(int device, const double* sos, const double* zi, int n_s
               "par_sosfiltfilt_f64: the length of the input vector x must be greater than padlen, which is %lld",
               (long long)padlen);   // scipy's own ValueError text
   PAR_REQUIRE(work_len >= par_sosfiltfilt_work_len(n, padlen), PAR_ERR_WORKSPACE, "par_sosfiltfilt_f64: workspace too small");
+  for (int sec = 0; sec < n_sections; ++sec)
+    PAR_REQUIRE(sos[6 * sec + 3] == 1.0, PAR_ERR_ARG, "par_sosfiltfilt_f64: sos[%d,3] (a0) must be 1", sec);
   PAR_HIP_CHECK(hipSetDevice(device));
   hipStream_t st = as_stream(stream);
   const int64_t L = n + 2 * padlen;
@@ -420,21 +483,9 @@ int par_sosfiltfilt_f64(int device, const double* sos, const double* zi, int n_s
     // zi scales with the first sample this pass consumes: ext[0] forward, y[L-1] backward
     for (int sec = 0; sec < n_sections; ++sec) {
       const double* c = sos + 6 * sec;
-      PAR_REQUIRE(c[3] == 1.0, PAR_ERR_ARG, "par_sosfiltfilt_f64: sos[%d,3] (a0) must be 1", sec);
       Biquad q{c[0], c[1], c[2], c[4], c[5]};
-      // P = A^kFiltBlock, A = [[-a1, 1], [-a2, 0]]
-      double p00 = 1, p01 = 0, p10 = 0, p11 = 1;
-      double a00 = -q.a1, a01 = 1.0, a10 = -q.a2, a11 = 0.0;
-      for (int e = kFiltBlock; e > 0; e >>= 1) {
-        if (e & 1) {
-          const double t00 = p00 * a00 + p01 * a10, t01 = p00 * a01 + p01 * a11;
-          const double t10 = p10 * a00 + p11 * a10, t11 = p10 * a01 + p11 * a11;
-          p00 = t00; p01 = t01; p10 = t10; p11 = t11;
-        }
-        const double s00 = a00 * a00 + a01 * a10, s01 = a00 * a01 + a01 * a11;
-        const double s10 = a10 * a00 + a11 * a10, s11 = a10 * a01 + a11 * a11;
-        a00 = s00; a01 = s01; a10 = s10; a11 = s11;
-      }
+      BlockMat P, Q;
+      block_matrices(q.a1, q.a2, P, Q);
       // the scale sample is the first element of the CASCADE input of this direction; after the first
       // section `cur` no longer holds it, so it is latched into work[-1] region (s tail) per direction.
       double* latch = s + 2 * nblk + (dir ? 1 : 0);
@@ -445,28 +496,15 @@ int par_sosfiltfilt_f64(int device, const double* sos, const double* zi, int n_s
       const bool tiled = L >= PAR_FILT_TILED_MIN;
       if (tiled) hipLaunchKernelGGL(k_sos_block_zero, dim3((unsigned)ceil_div(nblk, 64)), dim3(64), 0, st, cur, L, dir, q, nblk, r);
       else hipLaunchKernelGGL(k_sos_block_zero_direct, dim3((unsigned)ceil_div(nblk, 64)), dim3(64), 0, st, cur, L, dir, q, nblk, r);
-      if (nsup <= 4) {
-        hipLaunchKernelGGL(k_sos_chain, dim3(1), dim3(1), 0, st, r, nblk, p00, p01, p10, p11, zi[2 * sec], zi[2 * sec + 1],
-                           latch, s);
+      // one super-block: the plain chain IS the two-level chain (its middle level has one step).  From two on, the two-level
+      // chain, as the batched form runs it at every length: the rows of a batch equal single calls bit for bit
+      if (nsup <= 1) {
+        hipLaunchKernelGGL(k_sos_chain, dim3(1), dim3(1), 0, st, r, nblk, P, zi[2 * sec], zi[2 * sec + 1], latch, s);
       } else {
-        // Q = P^kFiltSuper
-        double q00 = 1, q01 = 0, q10 = 0, q11 = 1, b00 = p00, b01 = p01, b10 = p10, b11 = p11;
-        for (int e = kFiltSuper; e > 0; e >>= 1) {
-          if (e & 1) {
-            const double t00 = q00 * b00 + q01 * b10, t01 = q00 * b01 + q01 * b11;
-            const double t10 = q10 * b00 + q11 * b10, t11 = q10 * b01 + q11 * b11;
-            q00 = t00; q01 = t01; q10 = t10; q11 = t11;
-          }
-          const double s00 = b00 * b00 + b01 * b10, s01 = b00 * b01 + b01 * b11;
-          const double s10 = b10 * b00 + b11 * b10, s11 = b10 * b01 + b11 * b11;
-          b00 = s00; b01 = s01; b10 = s10; b11 = s11;
-        }
-        hipLaunchKernelGGL(k_sos_super_zero, dim3((unsigned)ceil_div(nsup, 64)), dim3(64), 0, st, (const double*)r, nblk, p00, p01,
-                           p10, p11, nsup, Rs);
-        hipLaunchKernelGGL(k_sos_chain, dim3(1), dim3(1), 0, st, (const double*)Rs, nsup, q00, q01, q10, q11, zi[2 * sec],
-                           zi[2 * sec + 1], latch, Ss);
-        hipLaunchKernelGGL(k_sos_super_run, dim3((unsigned)ceil_div(nsup, 64)), dim3(64), 0, st, (const double*)r, nblk, p00, p01,
-                           p10, p11, nsup, (const double*)Ss, s);
+        hipLaunchKernelGGL(k_sos_super_zero, dim3((unsigned)ceil_div(nsup, 64)), dim3(64), 0, st, (const double*)r, nblk, P, nsup, Rs);
+        hipLaunchKernelGGL(k_sos_chain, dim3(1), dim3(1), 0, st, (const double*)Rs, nsup, Q, zi[2 * sec], zi[2 * sec + 1], latch, Ss);
+        hipLaunchKernelGGL(k_sos_super_run, dim3((unsigned)ceil_div(nsup, 64)), dim3(64), 0, st, (const double*)r, nblk, P, nsup,
+                           (const double*)Ss, s);
       }
       if (tiled) hipLaunchKernelGGL(k_sos_block_run, dim3((unsigned)ceil_div(nblk, 64)), dim3(64), 0, st, cur, L, dir, q, nblk, s, nxt);
       else hipLaunchKernelGGL(k_sos_block_run_direct, dim3((unsigned)ceil_div(nblk, 64)), dim3(64), 0, st, cur, L, dir, q, nblk, s, nxt);
@@ -485,7 +523,7 @@ int64_t par_sosfiltfilt_batch_work_len(int64_t n, int64_t padlen, int n_sig, int
   const int64_t L = n + 2 * padlen;
   const int64_t nblk = (L + par::kFiltBlock - 1) / par::kFiltBlock;
   const int64_t nsup = (nblk + par::kFiltSuper - 1) / par::kFiltSuper;
-  return (int64_t)n_sig * (2 * L + 4 * nblk + 4 * nsup + 2) + (int64_t)n_sig * n_sections * 16 + 16;
+  return (int64_t)n_sig * (2 * L + 4 * nblk + 4 * nsup + 2) + (int64_t)n_sig * n_sections * par::kFiltParamDoubles + 16;
 }
 
 int par_sosfiltfilt_batch_f64(int device, const double* sos, const double* zi, int n_filt, int n_sections, const double* x,
@@ -503,6 +541,10 @@ int par_sosfiltfilt_batch_f64(int device, const double* sos, const double* zi, i
   PAR_REQUIRE(x_stride >= n && y_stride >= n, PAR_ERR_ARG, "par_sosfiltfilt_batch_f64: signal strides shorter than the signals");
   PAR_REQUIRE(work_len >= par_sosfiltfilt_batch_work_len(n, padlen, n_sig, n_sections), PAR_ERR_WORKSPACE,
               "par_sosfiltfilt_batch_f64: workspace too small");
+  for (int f = 0; f < n_filt; ++f)
+    for (int sec = 0; sec < n_sections; ++sec)
+      PAR_REQUIRE(sos[6 * ((size_t)f * n_sections + sec) + 3] == 1.0, PAR_ERR_ARG,
+                  "par_sosfiltfilt_batch_f64: sos[%d][%d,3] (a0) must be 1", f, sec);
   PAR_HIP_CHECK(hipSetDevice(device));
   hipStream_t st = as_stream(stream);
   const int64_t L = n + 2 * padlen;
@@ -518,23 +560,19 @@ int par_sosfiltfilt_batch_f64(int device, const double* sos, const double* zi, i
   FiltParam* fp = reinterpret_cast<FiltParam*>(latch + 2 * (int64_t)n_sig + ((2 * (int64_t)n_sig) & 1));   // 16-byte aligned
   // parameter table [n_sig][n_sections] (a shared cascade is replicated: the kernels index by signal)
   std::vector<FiltParam> host((size_t)n_sig * n_sections);
-  for (int sg = 0; sg < n_sig; ++sg) {
-    const int f = n_filt == 1 ? 0 : sg;
+  for (int f = 0; f < n_filt; ++f) {
     for (int sec = 0; sec < n_sections; ++sec) {
       const double* c = sos + 6 * ((size_t)f * n_sections + sec);
-      PAR_REQUIRE(c[3] == 1.0, PAR_ERR_ARG, "par_sosfiltfilt_batch_f64: sos[%d][%d,3] (a0) must be 1", f, sec);
-      FiltParam& q = host[(size_t)sg * n_sections + sec];
+      FiltParam& q = host[(size_t)f * n_sections + sec];
       q.b0 = c[0]; q.b1 = c[1]; q.b2 = c[2]; q.a1 = c[4]; q.a2 = c[5];
-      double P[4], Q[4];
-      mat_pow(-q.a1, 1.0, -q.a2, 0.0, kFiltBlock, P);
-      mat_pow(P[0], P[1], P[2], P[3], kFiltSuper, Q);
-      q.p00 = P[0]; q.p01 = P[1]; q.p10 = P[2]; q.p11 = P[3];
-      q.q00 = Q[0]; q.q01 = Q[1]; q.q10 = Q[2]; q.q11 = Q[3];
+      block_matrices(q.a1, q.a2, q.P, q.Q);
       q.zi0 = zi[2 * ((size_t)f * n_sections + sec)];
       q.zi1 = zi[2 * ((size_t)f * n_sections + sec) + 1];
       q.pad = 0.0;
     }
   }
+  if (n_filt == 1)
+    for (int sg = 1; sg < n_sig; ++sg) std::copy(host.begin(), host.begin() + n_sections, host.begin() + (size_t)sg * n_sections);
   PAR_HIP_CHECK(hipMemcpyAsync(fp, host.data(), host.size() * sizeof(FiltParam), hipMemcpyHostToDevice, st));
   PAR_HIP_CHECK(hipStreamSynchronize(st));                   // `host` is pageable and dies with this call
   const dim3 gL((unsigned)ceil_div(L, 256), (unsigned)n_sig), gB((unsigned)ceil_div(nblk, 64), (unsigned)n_sig),
