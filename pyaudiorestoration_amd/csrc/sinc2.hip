@@ -144,20 +144,21 @@ __device__ __forceinline__ float h_hi(unsigned w) { return (float)__builtin_bit_
 // read that might alias the destination gets an s_waitcnt vmcnt(0) in front of it -- the very latency the stream is built to
 // hide.  Issued this way the compiler does not count them; the kernel waits for them itself (one vmcnt(0) at the head of a
 // pass, when they are a whole pass old).
-__device__ __forceinline__ void dma_dword(const float* gptr, const void* lds) {
-  const unsigned la = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)lds;
+// The destination is a 32-bit LDS ADDRESS (lds_addr() of the stream's LDS, once per wave, plus a member's offset): handed over
+// as a generic pointer every call paid the cast's null check in front of its s_mov m0 (r09).
+__device__ __forceinline__ unsigned lds_addr(const void* lds) {
+  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)lds;
+}
+__device__ __forceinline__ void dma_dword(const float* gptr, const unsigned la) {
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off" ::"v"(gptr), "s"(__builtin_amdgcn_readfirstlane(la)) : "memory", "m0");
 }
-__device__ __forceinline__ void dma_dwordx4(const void* gptr, const void* lds) {
-  const unsigned la = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)lds;
+__device__ __forceinline__ void dma_dwordx4(const void* gptr, const unsigned la) {
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gptr), "s"(__builtin_amdgcn_readfirstlane(la)) : "memory", "m0");
 }
 
-// 128 consecutive floats from a wave-uniform address: two direct loads off a scalar base (per-lane byte offset 4 l; the instruction
+// 128 consecutive floats from a wave-uniform address (b, as an integer): two direct loads off a scalar base (per-lane byte offset 4 l; the instruction
 // offset advances the global and the LDS address alike)
-__device__ __forceinline__ void dma_chunk128(const float* base, unsigned lane_bytes, const void* lds) {
-  const unsigned la = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)lds;
-  const unsigned long long b = (unsigned long long)(uintptr_t)base;
+__device__ __forceinline__ void dma_chunk128(const unsigned long long b, unsigned lane_bytes, const unsigned la) {
   const unsigned long long bs = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
                                 (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);       // (the value IS wave-uniform)
   asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dword %0, %1\n\tglobal_load_lds_dword %0, %1 offset:256"
@@ -165,9 +166,7 @@ __device__ __forceinline__ void dma_chunk128(const float* base, unsigned lane_by
 }
 
 // 128 stereo frames (256 consecutive floats): four direct loads
-__device__ __forceinline__ void dma_chunk256(const float* base, unsigned lane_bytes, const void* lds) {
-  const unsigned la = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)lds;
-  const unsigned long long b = (unsigned long long)(uintptr_t)base;
+__device__ __forceinline__ void dma_chunk256(const unsigned long long b, unsigned lane_bytes, const unsigned la) {
   const unsigned long long bs = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
                                 (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
   asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dword %0, %1\n\tglobal_load_lds_dword %0, %1 offset:256\n\t"
@@ -460,54 +459,71 @@ __device__ __forceinline__ float s3_out_row(const LDS& L, const int ci, const fl
 
 // one chunk of the ring -> float16 images (and the ring's mirrors); returns false when float16 does not suit the chunk
 // (in two halves like a row's gather: the lane's two ring samples, and the arithmetic with the image writes)
+// A chunk is named by its first window index w0 = 128 x chunk (what the loop carries, r09).  The verdict is a lane MASK, zero
+// when float16 suits the chunk: bitwise on the three ballots, so that no branch is compiled for it and a caller can OR it
+// into its other masks.
+// The ring's mirrors -- frames 0 .. 3 behind frame 1023, frames 1022, 1023 in front of frame 0: each behind a scalar branch on
+// the chunk's slot with the lane test inside (six chunks in eight pass both by; as two exec-masked blocks they ran their mask
+// algebra in every iteration).
+__device__ __forceinline__ unsigned long long s3_convert_verdict(const float x0, const float x1) {
+  const float am = fmaxf(fabsf(x0), fabsf(x1));
+  const unsigned long long big = __ballot(!(fabsf(x0) < kImgMax) || !(fabsf(x1) < kImgMax));       // (also set for NaN)
+  const unsigned long long loud = __ballot(am >= kQuiet), some = __ballot(am > 0.0f);
+  return big | (loud == 0ull ? some : 0ull);
+}
+template <int NCH, class LDS, class V>
+__device__ __forceinline__ void s3_ring_mirrors(LDS& L, const int w0, const int l, const int ix, const V xx) {
+  const int slot = w0 & (7 * kPass);                        // (wave-uniform)
+  // (the wave barrier -- no instruction -- keeps the compiler from folding the slot test into the lane mask again)
+  if (slot == 0) {
+    __builtin_amdgcn_wave_barrier();
+    if (l < 2) *reinterpret_cast<V*>(&L.ring_tail[NCH * ix]) = xx;
+  }
+  if (slot == 7 * kPass) {
+    __builtin_amdgcn_wave_barrier();
+    if (l == kWave - 1) *reinterpret_cast<V*>(&L.ring_head[2 * NCH]) = xx;
+  }
+}
 template <class LDS>
-__device__ __forceinline__ float2 s3_convert_load(const LDS& L, const int chunk, const int l) {
-  const int ix = (chunk * kPass + 2 * l) & (kRingF - 1);
+__device__ __forceinline__ float2 s3_convert_load(const LDS& L, const int w0, const int l) {
+  const int ix = (w0 + 2 * l) & (kRingF - 1);
   return *reinterpret_cast<const float2*>(&L.ring[ix]);
 }
 template <class LDS>
-__device__ __forceinline__ bool s3_convert_math(LDS& L, const int chunk, const int l, const float2 xx) {
-  const int wi = chunk * kPass + 2 * l;
+__device__ __forceinline__ unsigned long long s3_convert_math(LDS& L, const int w0, const int l, const float2 xx) {
+  const int wi = w0 + 2 * l;
   const int ix = wi & (kRingF - 1), ih = wi & (kRingH - 1);
   const float x0 = xx.x, x1 = xx.y;
-  const float am = fmaxf(fabsf(x0), fabsf(x1));
-  const bool ok = !(__ballot(!(fabsf(x0) < kImgMax) || !(fabsf(x1) < kImgMax)) != 0ull ||       // (also false for NaN)
-                    (__ballot(am >= kQuiet) == 0ull && __ballot(am > 0.0f) != 0ull));
-  if ((chunk & 7) == 0 && l < 2) *reinterpret_cast<float2*>(&L.ring_tail[ix]) = xx;
-  if ((chunk & 7) == 7 && l == kWave - 1) *reinterpret_cast<float2*>(&L.ring_head[2]) = xx;
+  const unsigned long long trouble = s3_convert_verdict(x0, x1);
+  s3_ring_mirrors<1>(L, w0, l, ix, xx);
   const float s0 = x0 * kImgScale, s1 = x1 * kImgScale;
   const half2v h = {S2_HI(s0), S2_HI(s1)};
   const half2v lo = {(_Float16)((s0 - (float)h[0]) * 4096.0f), (_Float16)((s1 - (float)h[1]) * 4096.0f)};
   *reinterpret_cast<half2v*>(&L.img[0][ih]) = h;
   *reinterpret_cast<half2v*>(&L.img[1][ih]) = lo;
-  return ok;
+  return trouble;
 }
 template <class LDS>
-__device__ __forceinline__ bool s3_convert(LDS& L, const int chunk, const int l) {
-  return s3_convert_math(L, chunk, l, s3_convert_load(L, chunk, l));
+__device__ __forceinline__ unsigned long long s3_convert(LDS& L, const int w0, const int l) {
+  return s3_convert_math(L, w0, l, s3_convert_load(L, w0, l));
 }
 
 // Stereo ring (frames left, right): channel `ch` of one chunk -> that channel's float16 images.  `mirrors`: the call also keeps the
 // ring's mirror frames (both channels': the caller converts channel 0 of a chunk first).
 template <class LDS>
-__device__ __forceinline__ bool s3_convert_ch(LDS& L, const int chunk, const int l, const int ch, const bool mirrors) {
-  const int wi = chunk * kPass + 2 * l;
+__device__ __forceinline__ unsigned long long s3_convert_ch(LDS& L, const int w0, const int l, const int ch, const bool mirrors) {
+  const int wi = w0 + 2 * l;
   const int ix = wi & (kRingF - 1), ih = wi & (kRingH - 1);
   const float4v xx = *reinterpret_cast<const float4v*>(&L.ring[2 * ix]);
   const float x0 = ch ? xx[1] : xx[0], x1 = ch ? xx[3] : xx[2];
-  const float am = fmaxf(fabsf(x0), fabsf(x1));
-  const bool ok = !(__ballot(!(fabsf(x0) < kImgMax) || !(fabsf(x1) < kImgMax)) != 0ull ||
-                    (__ballot(am >= kQuiet) == 0ull && __ballot(am > 0.0f) != 0ull));
-  if (mirrors) {
-    if ((chunk & 7) == 0 && l < 2) *reinterpret_cast<float4v*>(&L.ring_tail[2 * ix]) = xx;
-    if ((chunk & 7) == 7 && l == kWave - 1) *reinterpret_cast<float4v*>(&L.ring_head[4]) = xx;
-  }
+  const unsigned long long trouble = s3_convert_verdict(x0, x1);
+  if (mirrors) s3_ring_mirrors<2>(L, w0, l, ix, xx);
   const float s0 = x0 * kImgScale, s1 = x1 * kImgScale;
   const half2v h = {S2_HI(s0), S2_HI(s1)};
   const half2v lo = {(_Float16)((s0 - (float)h[0]) * 4096.0f), (_Float16)((s1 - (float)h[1]) * 4096.0f)};
   *reinterpret_cast<half2v*>(&L.img[2 * ch][ih]) = h;
   *reinterpret_cast<half2v*>(&L.img[2 * ch + 1][ih]) = lo;
-  return ok;
+  return trouble;
 }
 
 // fc < 1 passes are fc = 1 + the moment correction (one image per channel, per-lane 1 - fc exact): valid for 1 - fc <= 0.0125,
@@ -627,7 +643,11 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
 
   // ---- stream state (wave-uniform) ----
   int j0 = 0;                                    // first output not yet placed into a finished pass
-  int wbase = 0, conv_next = 0, conv_lo = 0, dma_next = 0, dma_bad = INT_MAX, mode = 0, pk = 0;
+  // dma_bad: the first chunk of the ring that does not lie inside the file (set where the ring is restarted: chunks are issued
+  // in increasing order from 0, so it is known from the file's ends); capped well above any chunk a ring reaches (a ring is
+  // restarted 2^20 samples behind its base) so that 128 x dma_bad stays an int
+  constexpr int kDmaBadMax = 1 << 22;
+  int wbase = 0, conv_next = 0, conv_lo = 0, dma_next = 0, dma_bad = 0, mode = 0, pk = 0;
   int regime = 1;                                // the loop the current pass belongs to: 1 fc = 1, 2 / 3 fc = 1 + the moment correction to order 5 / 6
                                                  // (mode: 1 = the float16 images in LDS follow the ring, 0 = to be rebuilt)
   int rbA = 0, rbB = 0, rbC = 0;                 // first block (relative) of the record buffers of passes pk + 1, pk + 2, pk + 3
@@ -635,28 +655,35 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
   // records: lanes 0-7 fetch first pieces, 8-15 second pieces, one 16-byte direct load each.  (The plan's record arrays end four
   // tiles behind the file's last block -- fused_blocks(), pos_plan.h -- so the 16 blocks a guess may reach past it are readable.)
   const uint4* const rec_lane = (l < 8 ? recW : rec2W) + (l & 7);
-  auto fetch_records = [&](int buf, int blk0) {  // 8 first pieces + 8 second pieces from block blk0 on -> recs[buf]
-    if (l < 16) dma_dwordx4(rec_lane + (blk0 < 0 ? 0 : blk0), &L.recs[buf][0]);
+  using LdsT = S3Lds<NCH, KIND != 1>;
+  const unsigned lds_base = lds_addr(&L);        // direct loads name their LDS destination by address: one cast per wave
+  const unsigned lds_recs = lds_base + (unsigned)offsetof(LdsT, recs), lds_ring = lds_base + (unsigned)offsetof(LdsT, ring);
+  constexpr unsigned kRecBufBytes = 16 * sizeof(uint4);              // one pass's records in LDS
+  constexpr unsigned kChunkBytes = kPass * NCH * sizeof(float);      // one chunk of the ring, in LDS as in memory
+  // (rbytes: the buffer as its byte offset in L.recs, kRecBufBytes x (pass & 3) -- what the loop carries)
+  auto fetch_records_at = [&](unsigned rbytes, int blk0) {           // 8 first pieces + 8 second pieces from block blk0 on
+    if (l < 16) dma_dwordx4(rec_lane + (blk0 < 0 ? 0 : blk0), lds_recs + rbytes);
   };
-  // ring chunks: chunk k = input samples [wbase + 128 k, + 128) relative to A0 -> ring slot k & 7.  Chunks dma_klo .. dma_khi lie
-  // inside the file (set when the ring is restarted); the others are never used (dma_bad) and fetch some readable stretch instead.
-  int dma_klo = 0, dma_khi = -1;
-  const float* ring_src = a.sig;                 // &sig[A0 + wbase]
+  auto fetch_records = [&](int buf, int blk0) { fetch_records_at(kRecBufBytes * (unsigned)buf, blk0); };
+  // ring chunks: chunk k = input samples [wbase + 128 k, + 128) relative to A0 -> ring slot k & 7.  Chunks 0 .. dma_bad - 1 lie
+  // inside the file; the others are never used and fetch some readable stretch instead.
+  unsigned long long ring_src = (unsigned long long)(uintptr_t)a.sig;      // &sig[A0 + wbase], as an integer
   auto ring_restart = [&]() {
     const long long o = A0 + wbase;
-    ring_src = a.sig + NCH * o;
+    ring_src = (unsigned long long)(uintptr_t)a.sig + (unsigned long long)((long long)(NCH * sizeof(float)) * o);
     // (one channel of frames: the last frame's second word may lie one float behind the caller's view -- never fetched)
-    const long long klo = o >= 0 ? 0 : (-o + kPass - 1) / kPass, khi = ((long long)a.len_in - (kPick ? 1 : 0) - o) / kPass - 1;
-    dma_klo = (int)(klo > 0x3fffffff ? 0x3fffffff : klo);
-    dma_khi = (int)(khi > 0x3fffffff ? 0x3fffffff : (khi < -1 ? -1 : khi));
+    const long long khi = ((long long)a.len_in - (kPick ? 1 : 0) - o) / kPass - 1;      // last chunk that ends inside the file
+    dma_bad = o < 0 || khi < 0 ? 0 : (int)(khi + 1 > kDmaBadMax ? kDmaBadMax : khi + 1);
   };
   const unsigned lane_bytes = 4u * (unsigned)l;
-  auto chunk_dma = [&](int k) {
-    const bool inside = k >= dma_klo && k <= dma_khi;
-    if (!inside) dma_bad = k < dma_bad ? k : dma_bad;
-    const float* src = inside ? ring_src + (long long)(kPass * NCH) * k : a.sig;      // (a.sig: len_in >= 128 for every file this kernel is launched on)
-    if constexpr (NCH == 2) dma_chunk256(src, lane_bytes, &L.ring[(k & 7) * (kPass * 2)]);
-    else dma_chunk128(src, lane_bytes, &L.ring[(k & 7) * kPass]);
+  // (src: &chunk; the fallback a.sig is readable: len_in >= 128 for every file this kernel is launched on)
+  auto chunk_dma_at = [&](bool inside, unsigned long long src, unsigned slot_bytes) {
+    const unsigned long long s = inside ? src : (unsigned long long)(uintptr_t)a.sig;
+    if constexpr (NCH == 2) dma_chunk256(s, lane_bytes, lds_ring + slot_bytes);
+    else dma_chunk128(s, lane_bytes, lds_ring + slot_bytes);
+  };
+  auto chunk_dma = [&](int k) {                  // the cold path's form; the loop carries the source and the slot
+    chunk_dma_at(k < dma_bad, ring_src + (unsigned long long)((long long)kChunkBytes * k), (unsigned)(k & 7) * kChunkBytes);
   };
   auto push_tile = [&](int64_t T) {
     if (l == 0) {
@@ -673,29 +700,35 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     int fl0, fl1, tend;
     int epm;                                     // the larger period - 1 of the lane's two outputs, as its bit pattern (ep >= 0: ordered like the floats)
   };
-  int tc_T = -1, tc_dA0 = 0, tc_dA1 = 0, tc_fl0 = 0, tc_fl1 = 0;      // anchors and flags of the tile of j and of the one behind it (refreshed once per tile)
+  // anchors and flags of the tile of j and of the one behind it, refreshed once per tile.  j only ever grows over a wave's life,
+  // so "another tile" is j >= tc_tend (the cached tile's end; 0: nothing cached); tc_flm: the loop's exit margin of the two
+  // flags, negative for a flagged tile
+  int tc_tend = 0, tc_dA0 = 0, tc_dA1 = 0, tc_fl0 = 0, tc_fl1 = 0, tc_flm = 0;
   struct PlaceRecs {
     uint4 ra0, rb0, ra1, rb1;                    // first / second pieces of the blocks of the lane's two outputs
   };
-  auto place_load = [&](int j, int buf, int rb) {
+  // (rbytes: the record buffer as its byte offset in L.recs; jb = (j >> kRecShift) - rb, the pass's first block in the buffer --
+  // the loop's exit test needs it too, so the loop works it out once)
+  auto place_load = [&](int j, unsigned rbytes, int jb) {
     const int t5 = (j & (kRec - 1)) + l;
-    const int bi = ((j >> kRecShift) - rb + (t5 >> kRecShift)) & 7;
-    const uint4* rp = &L.recs[buf][0];
+    const int bi = (jb + (t5 >> kRecShift)) & 7;
+    const uint4* rp = &L.recs[0][0] + (rbytes >> 4);
     return PlaceRecs{rp[bi], rp[8 + bi], rp[(bi + 2) & 7], rp[8 + ((bi + 2) & 7)]};
   };
   // (EARLY: the records were read ahead by place_load; otherwise they are read here, where the compiler keeps the second pieces'
   // reads inside the variant that selects them)
-  auto place_impl = [&](int j, int buf, int rb, auto early, const PlaceRecs& RR) {
+  auto place_impl = [&](int j, unsigned rbytes, int jb, auto early, const PlaceRecs& RR) {
     Placed P;
-    const int T = j >> 10;
-    P.tend = (T + 1) << 10;
-    if (T != tc_T) {
-      tc_T = T;
+    if (j >= tc_tend) {
+      const int T = j >> 10;
+      tc_tend = (T + 1) << 10;
       tc_dA0 = __builtin_amdgcn_readlane(hd_dA, T);
       tc_dA1 = __builtin_amdgcn_readlane(hd_dA, T + 1);
       tc_fl0 = __builtin_amdgcn_readlane(hd_fl, T);
       tc_fl1 = __builtin_amdgcn_readlane(hd_fl, T + 1);
+      tc_flm = -((tc_fl0 | tc_fl1) & 1);
     }
+    P.tend = tc_tend;
     const int dA0 = tc_dA0, dA1 = tc_dA1;
     P.fl0 = tc_fl0;
     P.fl1 = tc_fl1;
@@ -705,14 +738,15 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     if constexpr (decltype(early)::value) {
       ra0 = RR.ra0, rb0 = RR.rb0, ra1 = RR.ra1, rb1 = RR.rb1;
     } else {
-      const int bi = ((j >> kRecShift) - rb + (t5 >> kRecShift)) & 7;
-      const uint4* rp = &L.recs[buf][0];
+      const int bi = (jb + (t5 >> kRecShift)) & 7;
+      const uint4* rp = &L.recs[0][0] + (rbytes >> 4);
       ra0 = rp[bi], rb0 = rp[8 + bi], ra1 = rp[(bi + 2) & 7], rb1 = rp[8 + ((bi + 2) & 7)];
     }
     const int uc = u - kRec / 2;
     const float uf = (float)uc, u2f = uf * uf, tw1 = fmaf(2.0f, uf, 1.0f), tw0 = tw1 - 2.0f;
-    P.nt[0] = clamp64(P.tend - j);
-    P.nt[1] = clamp64(P.tend - j - 64);
+    // lanes of the two rows that lie in the tile of j: l < nt[r] (a lane's compare needs no clamp; the cold path's masks clamp)
+    P.nt[0] = P.tend - j;
+    P.nt[1] = P.tend - j - 64;
     // a segment starts inside one block in eight: most passes have no second piece to select
     if (__ballot((unsigned)u > (ra0.x & 31u) || (unsigned)u > (ra1.x & 31u)) == 0ull) {
       P.R[0] = s2_place_row<false>(ra0, rb0, u, (l < P.nt[0] ? dA0 : dA1) + uc, uf, u2f, tw1, tw0, tolf);
@@ -726,7 +760,9 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     P.epm = max(__float_as_int(P.R[0].ep), __float_as_int(P.R[1].ep));
     return P;
   };
-  auto place = [&](int j, int buf, int rb) { return place_impl(j, buf, rb, std::false_type{}, PlaceRecs{}); };
+  auto place = [&](int j, int buf, int rb) {
+    return place_impl(j, kRecBufBytes * (unsigned)buf, (j >> kRecShift) - rb, std::false_type{}, PlaceRecs{});
+  };
 
   S3Pass P;                                      // the pass OUT works on next (placed, its bank in LDS)
   P.nok[0] = P.nok[1] = 0;
@@ -765,15 +801,16 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         reinterpret_cast<float2*>(outW)[(unsigned)Q.j + 64u * r + (unsigned)l] = make_float2(res0[r], res1[r]);
   };
   // one chunk of the ring -> float16 image(s); stereo: both channels of the chunk
-  auto convert_chunk = [&](int chunk) -> bool {
+  // (w0 = 128 x chunk; returns the lane mask of s3_convert_verdict: zero when the chunk suits float16)
+  auto convert_chunk = [&](int w0) -> unsigned long long {
     if constexpr (kPick) {
-      return s3_convert_ch(L, chunk, l, 0, true);
+      return s3_convert_ch(L, w0, l, 0, true);
     } else if constexpr (NCH == 2) {
-      const bool ok0 = s3_convert_ch(L, chunk, l, 0, true);
-      const bool ok1 = s3_convert_ch(L, chunk, l, 1, false);
-      return ok0 && ok1;
+      const unsigned long long t0 = s3_convert_ch(L, w0, l, 0, true);
+      const unsigned long long t1 = s3_convert_ch(L, w0, l, 1, false);
+      return t0 | t1;
     } else {
-      return s3_convert(L, chunk, l);
+      return s3_convert(L, w0, l);
     }
   };
 
@@ -802,11 +839,12 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       // the moment correction covers 1 - fc <= 0.0125
       const unsigned long long b0 = __ballot(Q.R[0].bad || !(Q.R[0].ep <= kEpMaxMom)) & prefix(nv[0]),
                                b1 = __ballot(Q.R[1].bad || !(Q.R[1].ep <= kEpMaxMom)) & prefix(nv[1]);
-      const unsigned long long bad_here = (b0 & prefix(Q.nt[0])) | (b1 & prefix(Q.nt[1]));
-      const bool bad_next = ((b0 & ~prefix(Q.nt[0])) | (b1 & ~prefix(Q.nt[1])) | (unsigned long long)((Q.fl1 & 1) && tend < nJ)) != 0ull;
+      const int nt0 = clamp64(Q.nt[0]), nt1 = clamp64(Q.nt[1]);
+      const unsigned long long bad_here = (b0 & prefix(nt0)) | (b1 & prefix(nt1));
+      const bool bad_next = ((b0 & ~prefix(nt0)) | (b1 & ~prefix(nt1)) | (unsigned long long)((Q.fl1 & 1) && tend < nJ)) != 0ull;
       if (bad_next) {                             // the pass ends at the tile border
-        nv[0] = nv[0] < Q.nt[0] ? nv[0] : Q.nt[0];
-        nv[1] = nv[1] < Q.nt[1] ? nv[1] : Q.nt[1];
+        nv[0] = nv[0] < nt0 ? nv[0] : nt0;
+        nv[1] = nv[1] < nt1 ? nv[1] : nt1;
       }
       bool skip = (Q.fl0 & 1) || bad_here != 0ull;
       const unsigned long long gen = (__ballot(1.0f + Q.R[0].ep != 1.0f) & prefix(nv[0])) | (__ballot(1.0f + Q.R[1].ep != 1.0f) & prefix(nv[1]));
@@ -833,9 +871,8 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
           __builtin_amdgcn_s_waitcnt(0x0F70);     // (nothing may still be on its way into the old ring)
           wbase = ws - 39;
           dma_next = 0;
-          dma_bad = INT_MAX;
           rebuild = true;
-          ring_restart();
+          ring_restart();                         // (names dma_bad for the new ring)
         }
         const int wsK = ws - wbase;
         regime = want;
@@ -871,7 +908,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
               skip = true;
               break;
             }
-            const bool ok = convert_chunk(conv_next);
+            const bool ok = convert_chunk(kPass * conv_next) == 0ull;
             if (!ok) {
               skip = true;
               break;
@@ -932,13 +969,30 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     // (the cold path left the loop's state in vector registers: it is wave-uniform, and stays so through the loop)
     j0 = __builtin_amdgcn_readfirstlane(j0);
     wbase = __builtin_amdgcn_readfirstlane(wbase);
-    conv_next = __builtin_amdgcn_readfirstlane(conv_next);
-    dma_next = __builtin_amdgcn_readfirstlane(dma_next);
-    dma_bad = __builtin_amdgcn_readfirstlane(dma_bad);
-    pk = __builtin_amdgcn_readfirstlane(pk);
     rbA = __builtin_amdgcn_readfirstlane(rbA);
     rbB = __builtin_amdgcn_readfirstlane(rbB);
     rbC = __builtin_amdgcn_readfirstlane(rbC);
+    tc_tend = __builtin_amdgcn_readfirstlane(tc_tend);
+    tc_flm = __builtin_amdgcn_readfirstlane(tc_flm);
+    // The pass counter, the conversion's chunk and the ring's next chunk advance in lockstep through the loop: ONE carried value,
+    // w0 = 128 x conv_next, and fixed differences to it (r09).  What the iteration needs of the three is carried in the form it is
+    // used in -- the record buffer as a byte offset, the next chunk's source address and ring slot as running values -- and the
+    // limits w0 is compared with are formed here, once per run: conv_next, dma_next and pk are named again where the loop leaves.
+    const int cn0 = __builtin_amdgcn_readfirstlane(conv_next), pk0 = __builtin_amdgcn_readfirstlane(pk);
+    const int dn0 = __builtin_amdgcn_readfirstlane(dma_next), dbad = __builtin_amdgcn_readfirstlane(dma_bad);
+    int w0 = kPass * cn0;
+    unsigned rbytes = kRecBufBytes * (unsigned)(pk0 & 3);
+    unsigned dslot = kChunkBytes * (unsigned)(dn0 & 7);
+    unsigned long long dsrc = ring_src + (unsigned long long)((long long)kChunkBytes * dn0);
+    dsrc = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(dsrc >> 32)) << 32) |
+           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)dsrc);
+    const int nJm = nJ - kPass;                  // j0 + kPass <= nJ
+    const int cn_lim = kPass * (dbad - 2);       // conv_next + 1 < dma_bad (the chunk the NEXT iteration converts was fetched from the file)
+    const int dn_lim = kPass * (dbad - (dn0 - cn0));      // dma_next < dma_bad, as a bound on w0
+    unsigned long long cok = 0ull;               // the conversion's verdict: zero when the chunk suits float16
+    // The loop's exit test is ONE signed margin m, the minimum of a margin per term: the pass stays in the loop while m >= 0
+    // (r09: a subtract and a minimum per term where every term was compare -> select -> AND of 64-bit masks).
+    int m = 0, adv = 0;                          // (adv: the outputs the placed pass finishes)
     for (;;) {
 #if PAR_S2_EXP & 64
       const unsigned long long tA_ = __builtin_readcyclecounter();
@@ -955,17 +1009,22 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       wave_lds_fence();
       // PLACE(pk): the pass behind P
       S3Pass N;
-      bool ok;
       int wsK;
+      const int jb = (j0 >> kRecShift) - rbA;     // the pass's first block in its record buffer: 0 or 1 where the guess held
       auto place_next = [&](auto early, const PlaceRecs& RR) {
-      const Placed Q = place_impl(j0, pk & 3, rbA, early, RR);
-      const unsigned long long bad = __ballot(Q.R[0].bad || Q.R[1].bad || Q.epm > __float_as_int(kEpMaxMom));
-      // some lane with fc < 1: 1 + ep != 1 in float32, i.e. ep > 2^-24 (ep >= 0)
-      const unsigned long long gen = __ballot(Q.epm > 0x33800000);          // 2^-24
-      // order 5 while no lane is steeper than 1 - fc = 0.0105; order 6 while some lane is above 0.95 of that
-      bool tier = true;
-      if constexpr (MODE == 2) tier = __ballot(Q.epm > __float_as_int(kEpMom5)) == 0ull;
-      if constexpr (MODE == 3) tier = __ballot(Q.epm > __float_as_int(kEpMom5Lo)) != 0ull;
+      const Placed Q = place_impl(j0, rbytes, jb, early, RR);
+      // The lane tests in two masks: `none` must be empty, `some` must not be.  With ep >= 0 as its bit pattern (epm):
+      //   none  a lane outside the record model or on a tie (bad), or too steep for the loop: epm > 2^-24 in the fc = 1 loop (1 + ep
+      //         != 1 in float32: a lane with fc < 1), > 0.0105 in the order-5 loop, > 0.0125 (the moment correction's limit)
+      //         in the order-6 loop -- each limit lies below the next, so one compare covers the lower ones' terms;
+      //   some  the loop's reason to be: a lane with fc < 1 in the order-5 loop, a lane above 0.95 x 0.0105 in the order-6 loop
+      //         (no flapping between the two; such a lane has fc < 1).
+      constexpr int kEpGen = 0x33800000;          // 2^-24
+      const int ep_hi = MODE == 1 ? kEpGen : (MODE == 2 ? __float_as_int(kEpMom5) : __float_as_int(kEpMaxMom));
+      const int n_none = __popcll(__ballot(Q.R[0].bad || Q.R[1].bad || Q.epm > ep_hi));
+      int n_some = 1;
+      if constexpr (MODE == 2) n_some = __popcll(__ballot(Q.epm > kEpGen));
+      if constexpr (MODE == 3) n_some = __popcll(__ballot(Q.epm > __float_as_int(kEpMom5Lo)));
       const int ws = __builtin_amdgcn_readfirstlane(Q.R[0].c) & ~7;
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
@@ -977,19 +1036,25 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       N.j = j0;
       N.ws = ws;
       wsK = ws - wbase;
-      const int d = kPass * conv_next - wsK;      // image converted up to d samples beyond the first bank centre
-      // (bitwise: one chain of scalar operations, no branch per term; >= 120 finished outputs imply a full first row)
-      ok = (((Q.fl0 | Q.fl1) & 1) == 0) & (bad == 0ull) & (j0 + kPass <= nJ) & (N.nok[0] + N.nok[1] >= 120) &
-           (MODE == 1 ? gen == 0ull : gen != 0ull) & tier & ((unsigned)(d - 161) <= 312u) & (conv_next + 1 < dma_bad) &
-           ((unsigned)((j0 >> kRecShift) - rbA) <= 1u);
+      const int d = w0 - wsK;                     // image converted up to d samples beyond the first bank centre
+      // neither tile flagged; the whole pass inside the range; >= 120 finished outputs (which imply a full first row);
+      // 161 <= d <= 473; the next chunk to convert came from the file; the records' guess held
+      // (the masks enter as lane COUNTS: a select on `mask == 0` is compiled as 64-bit mask algebra and a vector select.  A pass
+      // finishes <= 128 outputs, so 16 x n_none sinks that margin below zero whatever the pass finishes)
+      adv = N.nok[0] + N.nok[1];
+      m = min(tc_flm, nJm - j0);
+      m = min(m, adv - 120 - 16 * n_none);
+      m = min(m, min(d - 161, 473 - d));
+      m = min(m, cn_lim - w0);
+      m = min(m, min(jb, 1 - jb));
+      if constexpr (MODE != 1) m = min(m, n_some - 1);
       };
       float res[2];
-      bool cok;
       if constexpr (kEarly) {
         // The mono loop, every LDS read issued a stage ahead of its use (the order at the head of this kernel).  The reads whose
         // addresses the loop's state names: the records of PLACE(pk), the conversion's chunk, the gathers of OUT(P)
-        const PlaceRecs RR = place_load(j0, pk & 3, rbA);
-        const float2 cxx = s3_convert_load(L, conv_next, l);
+        const PlaceRecs RR = place_load(j0, rbytes, jb);
+        const float2 cxx = s3_convert_load(L, w0, l);
         S3Gather G[2];
         const int wsP = P.ws - wbase;
 #pragma unroll
@@ -1038,14 +1103,13 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         }
         // CONV's arithmetic and image writes (behind the fragment reads), then FETCH and the stores: five memory operations, in
         // this order
-        // (the loop's exit test is ~35 scalar instructions; left alone they all sink behind the stores, where the wave offers
-        // the vector port nothing: worked out here, beside the matrix work)
-        int oki = __builtin_amdgcn_readfirstlane((int)ok);
-        asm volatile("" : "+s"(oki));
-        ok = oki != 0;
-        cok = s3_convert_math(L, conv_next, l, cxx);
-        fetch_records((pk + 2) & 3, rbC);
-        chunk_dma(dma_next);
+        // (left alone the loop's exit test sinks behind the stores, where the wave offers the vector port nothing: worked out
+        // here, beside the matrix work)
+        m = __builtin_amdgcn_readfirstlane(m);
+        asm volatile("" : "+s"(m));
+        cok = s3_convert_math(L, w0, l, cxx);
+        fetch_records_at(rbytes ^ (2 * kRecBufBytes), rbC);
+        chunk_dma_at(w0 < dn_lim, dsrc, dslot);
         store_pass(P, res);
       } else {
       if constexpr (!kTwo) place_next(std::false_type{}, PlaceRecs{});      // (stereo: behind OUT(P, 1), fewer registers live through the banks)
@@ -1067,11 +1131,11 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         place_next(std::false_type{}, PlaceRecs{});
         const int offs = wsK - 31;
         bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, offs, l, 0);
-        const bool c0 = s3_convert_ch(L, conv_next, l, 0, true);
-        const bool c1 = s3_convert_ch(L, conv_next - 1, l, 1, false);
-        cok = c0 && c1;
-        fetch_records((pk + 2) & 3, rbC);
-        chunk_dma(dma_next);
+        const unsigned long long c0 = s3_convert_ch(L, w0, l, 0, true);
+        const unsigned long long c1 = s3_convert_ch(L, w0 - kPass, l, 1, false);
+        cok = c0 | c1;
+        fetch_records_at(rbytes ^ (2 * kRecBufBytes), rbC);
+        chunk_dma_at(w0 < dn_lim, dsrc, dslot);
         store_pass2(P, res, res1);
       } else {
         const int offs = wsK - 31;
@@ -1080,45 +1144,34 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
 #endif
         bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, offs, l);
         // CONV: one chunk per iteration
-        cok = convert_chunk(conv_next);
+        cok = convert_chunk(w0);
         // FETCH + stores: records of pass pk + 2, chunk conv_next + 2, then P's outputs (five memory operations, in this order)
-        fetch_records((pk + 2) & 3, rbC);
-        chunk_dma(dma_next);
+        fetch_records_at(rbytes ^ (2 * kRecBufBytes), rbC);
+        chunk_dma_at(w0 < dn_lim, dsrc, dslot);
         store_pass(P, res);
       }
       }
       wave_lds_fence();
-      ++conv_next;
-      ++dma_next;
-      if (!cok) mode = 0;                         // (start_run converts again and sends the tile to the block kernel)
+      w0 += kPass;
+      dsrc += kChunkBytes;
+      dslot = (dslot + kChunkBytes) & (8 * kChunkBytes - 1);
       S3_COUNT(2);
-#if PAR_S2_EXP & 128
-      if (!(ok && cok)) {
-        if (((Q.fl0 | Q.fl1) & 1) != 0 || bad != 0ull) S3_COUNT(3);
-        else if (!(j0 + kPass <= nJ)) S3_COUNT(4);
-        else if (!(N.nok[1] >= 1 && N.nok[0] + N.nok[1] >= 120)) S3_COUNT(5);
-        else if (!(MODE == 1 ? gen == 0ull : gen != 0ull)) S3_COUNT(6);
-        else if (!(d >= 161 && d <= 473)) S3_COUNT(7);
-        else if (!(conv_next < dma_bad)) S3_COUNT(9);
-        else if (!((unsigned)((j0 >> kRecShift) - rbA) <= 1u)) S3_COUNT(11);
-        else if (!cok) S3_COUNT(10);
-        else S3_COUNT(8);
-      }
-#endif
-      if (!(ok && cok)) {
-        // stereo: channel 1's image catches up with channel 0's before the cold path takes over
-        if constexpr (kTwo)
-          if (mode != 0 && !s3_convert_ch(L, conv_next - 1, l, 1, false)) mode = 0;
-        return;
-      }
+      if (min(m, -(int)__popcll(cok)) < 0) break;
       // N becomes P
       P = N;
-      j0 += N.nok[0] + N.nok[1];
-      ++pk;
+      j0 += adv;
+      rbytes = (rbytes + kRecBufBytes) & (3 * kRecBufBytes);
       rbA = rbB;
       rbB = rbC;
       rbC = (j0 + 240) >> kRecShift;
     }
+    conv_next = w0 >> 7;                          // (the pass that left the loop converted its chunk and was not counted)
+    dma_next = dn0 + (conv_next - cn0);
+    pk = pk0 + (conv_next - cn0) - 1;
+    if (cok != 0ull) mode = 0;                    // (start_run converts again and sends the tile to the block kernel)
+    // stereo: channel 1's image catches up with channel 0's before the cold path takes over
+    if constexpr (kTwo)
+      if (mode != 0 && s3_convert_ch(L, w0 - kPass, l, 1, false) != 0ull) mode = 0;
   };
 
   while (start_run()) {

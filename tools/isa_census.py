@@ -26,8 +26,10 @@ def stage_table(src):
     T = []
     for name, pat in (("place_row", r"S2Row s2_place_row"), ("bank", r"void bank_image3m"), ("out_row", r"float s3_out_row"),
                       ("bank", r"S3Frags bank_load"), ("bank", r"void bank_math"), ("out_row", r"S3Gather s3_out_load"),
-                      ("out_row", r"float s3_out_math"), ("convert", r"float2 s3_convert_load"), ("convert", r"bool s3_convert_math"),
-                      ("convert", r"bool s3_convert\("), ("convert", r"bool s3_convert_ch\("), ("out_row", r"float sinpi_poly")):
+                      ("out_row", r"float s3_out_math"), ("convert", r"float2 s3_convert_load"), ("convert", r"(bool|unsigned long long) s3_convert_math"),
+                      ("convert", r"(bool|unsigned long long) s3_convert\("), ("convert", r"(bool|unsigned long long) s3_convert_ch\("),
+                      ("convert", r"unsigned long long s3_convert_verdict"), ("convert", r"void s3_ring_mirrors"),
+                      ("out_row", r"float sinpi_poly")):
         try:
             a = find(r"__device__ __forceinline__ " + pat) if "S2Row" not in pat else find(pat)
         except KeyError:          # (a source from before the load / arithmetic halves: PAR_CSRC below)
@@ -43,7 +45,9 @@ def stage_table(src):
     T.append((a, b - 1, "out_pass"))
     a = find(r"auto store_pass = \[&\]"); b = find(r"auto convert_chunk", a)
     T.append((a, b - 1, "store"))
-    a = find(r"auto fetch_records = \[&\]"); b = find(r"auto push_tile", a)
+    try: a = find(r"auto fetch_records_at = \[&\]")
+    except KeyError: a = find(r"auto fetch_records = \[&\]")      # (a source from before r09)
+    b = find(r"auto push_tile", a)
     T.append((a, b - 1, "fetch"))
     for name, pat in (("dma", r"void dma_dword\("), ("dma", r"void dma_dwordx4"), ("dma", r"void dma_chunk128"), ("dma", r"void dma_chunk256"),
                       ("fence", r"void wave_lds_fence")):
@@ -147,11 +151,45 @@ def kernel_loops(L, nch, kind):
         # loop header: the nearest "Parent Loop" label above the head; body: every block that names it as its header
         hl = next(i for i in range(h, start, -1) if re.match(r"^\.LBB\d+_\d+:.*Parent Loop", L[i]))
         lab = L[hl].split(":")[0].lstrip(".L")
-        # the latch is the block in front of the header (it falls through into it); the body ends at the last branch to the latch
+        # the body ends at its last back edge: a branch to the header itself or, where the compiler has laid a latch in front of
+        # the header (a block that falls through into it), the last branch to that latch
+        head = L[hl].split(":")[0]
         latch = next(L[i].split(":")[0] for i in range(hl - 1, start, -1) if re.match(r"^\.LBB\d+_\d+:", L[i]))
-        back = max(i for i in range(hl, end) if re.search(r"s_c?branch\w*\s+%s\b" % re.escape(latch), L[i]))
+        to = lambda lab: [i for i in range(hl, end) if re.search(r"s_c?branch\w*\s+%s\b" % re.escape(lab), L[i])]
+        back = max(to(head) or to(latch))
         loops.append((hl, back))
     return info, loops
+
+def loop_census(L, h, back, files, stages, hi=None, dump=None):
+    """{stage: {class: instructions, "port": priced port cycles}} of one hot loop (listing lines h..back); dump: list that
+    stage's vector instructions"""
+    cur, last_stage = ("?", 0), "loop"
+    tab = {}
+    for i in range(h, back + 1):
+        l = L[i].strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", l)
+        if m: cur = (files.get(int(m.group(1)), "?"), int(m.group(2))); continue
+        if not l or l.startswith((";", ".", "//")) or l.endswith(":"): continue
+        op = l.split()[0]
+        if cur[0] == "sinc2.hip":
+            st = next((n for a, b, n in stages if a <= cur[1] <= b), "loop")
+            last_stage = st
+        else:
+            st = last_stage
+        cls = next(c for c, p in CLASS if re.match(p, op))
+        tab.setdefault(st, {}).setdefault(cls, 0)
+        tab[st][cls] += 1
+        tab[st]["port"] = tab[st].get("port", 0.0) + port_cycles(l)
+        if dump == st and cls in ("valu", "trans", "mfma"):
+            print(f"   [{hi}] {cur[1]:5d} {port_cycles(l):4.1f}  {l}")
+    return tab
+
+def loop_totals(tab):
+    """{class: instructions} of a loop_census() table, summed over the stages"""
+    tot = {}
+    for v in tab.values():
+        for c, n in v.items(): tot[c] = tot.get(c, 0) + n
+    return tot
 
 def main():
     waits = "--waits" in sys.argv
@@ -176,25 +214,7 @@ def main():
             print(f"matrix stretch: {n} MFMAs, {seq.count('v')} vector instructions between the first and the last, "
                   f"{sum(1 for b in behind if b >= 2)} MFMAs with two or more behind them\n  {seq}")
             continue
-        cur, last_stage = ("?", 0), "loop"
-        tab = {}
-        for i in range(h, back + 1):
-            l = L[i].strip()
-            m = re.match(r"\.loc\s+(\d+)\s+(\d+)", l)
-            if m: cur = (files.get(int(m.group(1)), "?"), int(m.group(2))); continue
-            if not l or l.startswith((";", ".", "//")) or l.endswith(":"): continue
-            op = l.split()[0]
-            if cur[0] == "sinc2.hip":
-                st = next((n for a, b, n in stages if a <= cur[1] <= b), "loop")
-                last_stage = st
-            else:
-                st = last_stage
-            cls = next(c for c, p in CLASS if re.match(p, op))
-            tab.setdefault(st, {}).setdefault(cls, 0)
-            tab[st][cls] += 1
-            tab[st]["port"] = tab[st].get("port", 0.0) + port_cycles(l)
-            if dump == st and cls in ("valu", "trans", "mfma"):
-                print(f"   [{hi}] {cur[1]:5d} {port_cycles(l):4.1f}  {l}")
+        tab = loop_census(L, h, back, files, stages, hi if dump else None, dump)
         n_mfma = sum(v.get("mfma", 0) for v in tab.values())
         what = "fc = 1" if n_mfma <= 16 else ("fc < 1, moment correction to order 5 (1 - fc <= 0.0105)" if n_mfma <= 29 else "fc < 1, moment correction to order 6")
         print(f"\nloop {hi} ({what}): listing lines {h}..{back}  [static; the placement's "
