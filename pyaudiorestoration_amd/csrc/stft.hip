@@ -23,14 +23,8 @@
 #include <math.h>
 #include <map>
 #include <set>
+#include <type_traits>
 #include <vector>
-
-#ifndef PAR_STFT_TW
-#define PAR_STFT_TW 0
-#endif
-#ifndef PAR_STFT_STORE
-#define PAR_STFT_STORE 0
-#endif
 
 namespace par {
 
@@ -45,10 +39,20 @@ static std::mutex g_tw_mu;
 static int raise_dynamic_lds(const void* fn, int bytes, int device) {
   static std::mutex mu;
   static std::set<std::pair<const void*, int>> done;
+  if (bytes <= 65536) return PAR_OK;
   std::lock_guard<std::mutex> lk(mu);
-  if (bytes <= 65536 || done.count({fn, device})) return PAR_OK;
+  if (done.count({fn, device})) return PAR_OK;
   PAR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   done.insert({fn, device});
+  return PAR_OK;
+}
+// launch with `lds` bytes of dynamic LDS, the kernel's limit raised first where the launch needs it
+template <typename... P, typename... A>
+static int launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, int device, hipStream_t s, A... args) {
+  const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds, device);
+  if (rc != PAR_OK) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }
 static std::map<std::pair<int, int>, Twiddles> g_tw;
@@ -181,17 +185,8 @@ __device__ __forceinline__ void fft_core(float2 (&v)[8], float2* __restrict__ X,
     if (st > 0) {
       // one gathered twiddle load per stage; the other six are its powers (3 multiply levels, ~2 ulp)
       const float2 w1 = w1s[st];
-#if PAR_STFT_TW == 1          // accuracy experiment: all seven from the table (correctly rounded)
-      const int ti = (j & (Ns - 1)) * (H / (Ns * 8));
-      const float2 w2 = tw[2 * ti], w3 = tw[3 * ti], w4 = tw[4 * ti], w5 = tw[5 * ti], w6 = tw[6 * ti], w7 = tw[7 * ti];
-#elif PAR_STFT_TW == 2        // accuracy experiment: w1, w2, w4 from the table, the rest one multiply away
-      const int ti = (j & (Ns - 1)) * (H / (Ns * 8));
-      const float2 w2 = tw[2 * ti], w4 = tw[4 * ti];
-      const float2 w3 = cmul(w2, w1), w5 = cmul(w4, w1), w6 = cmul(w4, w2), w7 = cmul(w4, w3);
-#else
       const float2 w2 = cmul(w1, w1), w3 = cmul(w2, w1), w4 = cmul(w2, w2);
       const float2 w5 = cmul(w4, w1), w6 = cmul(w3, w3), w7 = cmul(w4, w3);
-#endif
       v[1] = cmul(v[1], w1);
       v[2] = cmul(v[2], w2);
       v[3] = cmul(v[3], w3);
@@ -249,7 +244,32 @@ struct FftGeom {
   static constexpr int Threads = T > 256 ? T : 256;
   static constexpr int Frames = Threads / T;                    // frames per workgroup
   static constexpr int FrameLds = H + H / 8 + 8;                // padded float2 slots per frame
+  static constexpr int P = (H / 2) / T;                         // bin pairs (k, H - k) a lane untangles: k = j + i T, i < P
+  static constexpr size_t FramesLds = (size_t)Frames * FrameLds * sizeof(float2);    // bytes of LDS of a workgroup's frames
+  // workgroups for `items` frame slots: a multiple of the XCD count (xcd_contiguous_block)
+  static unsigned grid(int64_t items) { return (unsigned)(ceil_div(ceil_div(items, Frames), kXcds) * kXcds); }
 };
+
+// The kernels take the transform size as log2 of H = M / 2: f(std::integral_constant<int, LOGH>{}) for LOGH = logh in [LO, HI],
+// the sizes the caller's kernels exist for
+template <int LO, int HI, typename F>
+static int dispatch_logh(int logh, F&& f) {
+  if constexpr (LO > HI) {
+    PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "stft: no kernel for transforms of 2^%d points", logh + 1);
+  } else {
+    return logh == LO ? f(std::integral_constant<int, LO>{}) : dispatch_logh<LO + 1, HI>(logh, f);
+  }
+}
+// ... and a run-time flag as a bool template argument: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+static int dispatch_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+static int ilog2(int v) {
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return l;
+}
 
 // MODE 0: complex spectrum, 1: magnitude |X| + 1e-7, 2: band dB -- out[f] (float64, `out` reinterpreted) = mean over
 // b in [bin_l, bin_u) of 20 log10(the float32 magnitude mode 1 writes), with the band packed into `pitch` as
@@ -326,10 +346,6 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __
   const float hs = 0.5f * scale;
   const int band_l = (int)(pitch & 0xffffffffll), band_u = (int)(pitch >> 32);    // mode 2 only
   double band_acc = 0.0;
-  // PAR_STFT_STORE (experiment switch): 0 streaming (nontemporal) stores straight from the registers; 1 plain stores;
-  // 3 one-wave-per-frame sizes stage the row in the wave's own LDS and write it with 16-byte aligned stores
-  constexpr bool kRowStage = (PAR_STFT_STORE == 3) && T == kWave;
-  float* Mg = reinterpret_cast<float*>(lds + G::Frames * G::FrameLds) + f * (bins + 3);      // this frame's row (mode 1)
   // (re, im) arrive UNSCALED (twice the bin, before the 1/sqrt(n_fft)): the complex form scales both parts, the magnitude
   // form scales once behind the square root (|hs z| = hs |z|: two multiplies per bin saved)
   auto emit = [&](int k, float re, float im) {
@@ -347,8 +363,7 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __
       // streaming stores pay when a frame's lanes write runs of at least 64 bytes (T >= 16: n_fft >= 256); shorter runs only
       // complete their lines together with the neighbouring frames', in L2, and went to HBM piecemeal as streaming stores
       // (n_fft = 64, hop 16 on 57.6 M samples: 0.81 ms streaming, 0.39 ms plain; n_fft = 256: 0.26 against 0.31)
-      if (kRowStage) Mg[k] = mag;
-      else if (PAR_STFT_STORE == 1 || T < 16) out[fr * pitch + k] = mag;
+      if (T < 16) out[fr * pitch + k] = mag;
       else __builtin_nontemporal_store(mag, out + fr * pitch + k);
     }
   };
@@ -372,20 +387,6 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft(const float* __
     const float2 t = cmul(pw[i], csub(zk, zc));         // W^k * (Z[k] - conj(Z[H-k]))
     emit(k, ev.x + t.y, ev.y - t.x);                    // X[k]   = (ev - i*t)/2 * scale
     if (i < P) emit(H - k, ev.x - t.y, -ev.y - t.x);    // X[H-k] = (conj(ev) - i*conj(t))/2 * scale
-  }
-  if (kRowStage && mode == 1) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    typedef float vf4 __attribute__((ext_vector_type(4)));
-    const int64_t e0 = fr * pitch, e1 = e0 + bins;
-    const int64_t a0 = (e0 + 3) & ~3ll, a1 = e1 & ~3ll;
-    for (int64_t e = a0 + 4 * j; e < a1; e += 4 * T) {
-      const float* m = Mg + (e - e0);
-      const vf4 q = {m[0], m[1], m[2], m[3]};
-      __builtin_nontemporal_store(q, reinterpret_cast<vf4*>(out + e));
-    }
-    if (j < a0 - e0) __builtin_nontemporal_store(Mg[j], out + e0 + j);
-    if (j < e1 - a1) __builtin_nontemporal_store(Mg[a1 - e0 + j], out + a1 + j);
   }
   if constexpr (mode == 2) {
     // the frame's T lanes sum in a fixed order: xor butterflies inside the wave, then (T > 64) the waves' partials in
@@ -1890,23 +1891,17 @@ template <int LOGH>
 static inline size_t istft_fused_lds(int hop) {
   using G = FftGeom<LOGH>;
   const int64_t n_fft = 2 * G::H, s = (n_fft + hop - 1) / hop;
-  return (size_t)G::Frames * G::FrameLds * sizeof(float2) + (size_t)((G::Frames * s - 1) * hop + n_fft) * sizeof(float) +
+  return G::FramesLds + (size_t)((G::Frames * s - 1) * hop + n_fft) * sizeof(float) +
          (istft_tables_in_lds(LOGH) ? (size_t)n_fft * sizeof(float) + (size_t)G::H * sizeof(float2) : 0);   // + the tables
 }
 static inline size_t istft_fused_lds_any(int n_fft, int hop) {
-  switch (n_fft) {
-    case 16: return istft_fused_lds<3>(hop);
-    case 32: return istft_fused_lds<4>(hop);
-    case 64: return istft_fused_lds<5>(hop);
-    case 128: return istft_fused_lds<6>(hop);
-    case 256: return istft_fused_lds<7>(hop);
-    case 512: return istft_fused_lds<8>(hop);
-    case 1024: return istft_fused_lds<9>(hop);
-    case 2048: return istft_fused_lds<10>(hop);
-    case 4096: return istft_fused_lds<11>(hop);
-    case 8192: return istft_fused_lds<12>(hop);
-  }
-  return (size_t)-1;
+  size_t lds = (size_t)-1;
+  if (n_fft >= 16 && (n_fft & (n_fft - 1)) == 0)
+    (void)dispatch_logh<3, 12>(ilog2(n_fft / 2), [&](auto lh) {
+      lds = istft_fused_lds<decltype(lh)::value>(hop);
+      return PAR_OK;
+    });
+  return lds;
 }
 // Largest n_fft that takes the fused kernel.  A workgroup re-transforms s - 1 = n_fft/hop - 1 frames of its neighbour; with
 // 8 or 4 frames side by side (n_fft <= 1024) that is 13-23 % extra work for never storing the frames, at 2048 (2 frames)
@@ -1968,7 +1963,7 @@ struct GateGeom {
     return r;
   }
   static size_t lds(int hop) {
-    return (size_t)G::Frames * G::FrameLds * sizeof(float2) + (size_t)(ring(hop) + hop) * sizeof(float);
+    return G::FramesLds + (size_t)(ring(hop) + hop) * sizeof(float);
   }
   // Waves per SIMD the register allocation must keep (the second __launch_bounds__ argument).  The 2048- and 8192-point kernels
   // sit at 168 VGPRs, the last count at which three waves fit; the correctly rounded square root of gate_mag took them to 169 and
@@ -2168,10 +2163,15 @@ int64_t par_stft_frames(int64_t n, int n_fft, int hop) {
   return (n + 2 * (int64_t)(n_fft / 2) - n_fft) / hop + 1;
 }
 
-static int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
+// The register path's transform sizes: M = n_fft * zeropad a power of two in [16, 16384] of an even n_fft
+static bool stft_size_supported(int n_fft, int zeropad) {
+  const int64_t M = (int64_t)n_fft * zeropad;
+  return n_fft >= 2 && zeropad >= 1 && (n_fft % 2) == 0 && M >= 16 && M <= 16384 && (M & (M - 1)) == 0;
+}
+static int require_stft_size(const char* who, int n_fft, int zeropad) {
+  PAR_REQUIRE(stft_size_supported(n_fft, zeropad), PAR_ERR_UNSUPPORTED, "%s: n_fft*zeropad=%lld is not a power of two in [16, 16384]", who,
+              (long long)n_fft * zeropad);
+  return PAR_OK;
 }
 
 int par_stft_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, int zeropad,
@@ -2182,57 +2182,27 @@ int par_stft_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_
   PAR_REQUIRE(pitch >= (int64_t)n_fft * zeropad / 2 + 1, PAR_ERR_ARG, "par_stft_f32: out_pitch %lld < bins", (long long)out_pitch);
   PAR_REQUIRE(n >= 1 && x_stride >= 1 && hop >= 1 && zeropad >= 1 && n_fft >= 2, PAR_ERR_ARG, "par_stft_f32: bad sizes");
   PAR_REQUIRE(mode == 0 || mode == 1, PAR_ERR_ARG, "par_stft_f32: mode must be 0 (complex) or 1 (magnitude)");
-  const int64_t M64 = (int64_t)n_fft * zeropad;
-  PAR_REQUIRE(M64 >= 16 && M64 <= 16384 && (M64 & (M64 - 1)) == 0 && (n_fft % 2) == 0, PAR_ERR_UNSUPPORTED,
-              "par_stft_f32: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)M64);
-  const int M = (int)M64, H = M / 2;
+  int rc = require_stft_size("par_stft_f32", n_fft, zeropad);
+  if (rc != PAR_OK) return rc;
+  const int M = n_fft * zeropad, H = M / 2;
   PAR_HIP_CHECK(hipSetDevice(device));
   Twiddles tw;
-  int rc = get_twiddles(device, M, &tw);
+  rc = get_twiddles(device, M, &tw);
   if (rc != PAR_OK) return rc;
   const int64_t n_frames = par_stft_frames(n, n_fft, hop);
   const float scale = (float)(1.0 / sqrt((double)n_fft));
-#define PAR_STFT_LAUNCH_MU(LH, MD, UN)                                                                              \
-  hipLaunchKernelGGL((k_stft<LH, MD, UN>), dim3((unsigned)(ceil_div(ceil_div(n_frames, FftGeom<LH>::Frames), 8) * 8)), dim3(FftGeom<LH>::Threads),  \
-                     (size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2) +                              \
-                         (PAR_STFT_STORE == 3 ? (size_t)FftGeom<LH>::Frames * ((1 << LH) + 4) * sizeof(float) : 0),      \
-                     as_stream(stream), x, n, x_stride, n_fft, hop, window, tw.w, tw.post, out, n_frames, scale, pitch)
-#define PAR_STFT_LAUNCH(LH)                                                                                          \
-  do {                                                                                                               \
-    if (mode == 1 && x_stride == 1) PAR_STFT_LAUNCH_MU(LH, 1, true);                                                 \
-    else if (mode == 1) PAR_STFT_LAUNCH_MU(LH, 1, false);                                                            \
-    else if (x_stride == 1) PAR_STFT_LAUNCH_MU(LH, 0, true);                                                         \
-    else PAR_STFT_LAUNCH_MU(LH, 0, false);                                                                           \
-  } while (0)
-  switch (ilog2(H)) {
-    case 3: PAR_STFT_LAUNCH(3); break;
-    case 4: PAR_STFT_LAUNCH(4); break;
-    case 5: PAR_STFT_LAUNCH(5); break;
-    case 6: PAR_STFT_LAUNCH(6); break;
-    case 7: PAR_STFT_LAUNCH(7); break;
-    case 8: PAR_STFT_LAUNCH(8); break;
-    case 9: PAR_STFT_LAUNCH(9); break;
-    case 10: PAR_STFT_LAUNCH(10); break;
-    case 11: PAR_STFT_LAUNCH(11); break;
-    case 12: PAR_STFT_LAUNCH(12); break;
-    case 13: {
-      // 16384 points (the GUI's 4096 x zero-padding 4): one 1024-lane workgroup per frame, 72 KB of the CU's 160 KB of LDS
-      // (above the 64 KB a kernel gets by default: raised per kernel once)
-      constexpr int kLds13 = FftGeom<13>::Frames * FftGeom<13>::FrameLds * (int)sizeof(float2) + (PAR_STFT_STORE == 3 ? (8192 + 4) * 4 : 0);
-      for (const void* fn : {reinterpret_cast<const void*>(&k_stft<13, 0, true>), reinterpret_cast<const void*>(&k_stft<13, 0, false>),
-                             reinterpret_cast<const void*>(&k_stft<13, 1, true>), reinterpret_cast<const void*>(&k_stft<13, 1, false>)}) {
-        const int rc = raise_dynamic_lds(fn, kLds13, device);
-        if (rc != PAR_OK) return rc;
-      }
-      PAR_STFT_LAUNCH(13);
-      break;
-    }
-    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_f32: unsupported size");
-  }
-#undef PAR_STFT_LAUNCH
-#undef PAR_STFT_LAUNCH_MU
-  PAR_HIP_CHECK(hipGetLastError());
-  return PAR_OK;
+  // (16384 points -- the GUI's 4096 x zero-padding 4 -- are one 1024-lane workgroup per frame and 72 KB of the CU's 160 KB of
+  // LDS, above the 64 KB a kernel gets by default: raised per kernel once, here and in the fused consumers below)
+  return dispatch_logh<3, 13>(ilog2(H), [&](auto lh) {
+    return dispatch_bool(mode == 1, [&](auto mag) {
+      return dispatch_bool(x_stride == 1, [&](auto unit) {
+        using G = FftGeom<decltype(lh)::value>;
+        return launch_with_lds(k_stft<decltype(lh)::value, decltype(mag)::value ? 1 : 0, decltype(unit)::value>, dim3(G::grid(n_frames)),
+                               dim3(G::Threads), G::FramesLds, device, as_stream(stream), x, n, x_stride, n_fft, hop, window, tw.w, tw.post,
+                               out, n_frames, scale, pitch);
+      });
+    });
+  });
 }
 
 // Band dB straight out of the register-path transform (k_stft mode 2): out[f] = mean over b in [bin_l, bin_u) of
@@ -2245,54 +2215,26 @@ int par_stft_band_db_f32(int device, const float* x, int64_t n, int64_t x_stride
   const int64_t M64 = (int64_t)n_fft * zeropad;
   PAR_REQUIRE(0 <= bin_l && bin_l < bin_u && (int64_t)bin_u <= M64 / 2 + 1, PAR_ERR_ARG,
               "par_stft_band_db_f32: empty or out-of-range band [%d, %d) of %lld bins", bin_l, bin_u, (long long)(M64 / 2 + 1));
-  PAR_REQUIRE(M64 >= 16 && M64 <= 16384 && (M64 & (M64 - 1)) == 0 && (n_fft % 2) == 0, PAR_ERR_UNSUPPORTED,
-              "par_stft_band_db_f32: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)M64);
+  int rc = require_stft_size("par_stft_band_db_f32", n_fft, zeropad);
+  if (rc != PAR_OK) return rc;
   const int M = (int)M64, H = M / 2;
   PAR_HIP_CHECK(hipSetDevice(device));
   Twiddles tw;
-  int rc = get_twiddles(device, M, &tw);
+  rc = get_twiddles(device, M, &tw);
   if (rc != PAR_OK) return rc;
   const int64_t n_frames = par_stft_frames(n, n_fft, hop);
   const float scale = (float)(1.0 / sqrt((double)n_fft));
   const int64_t band = (int64_t)bin_l | ((int64_t)bin_u << 32);
   float* outf = reinterpret_cast<float*>(out);
-#define PAR_BAND_LAUNCH_U(LH, UN)                                                                                       \
-  hipLaunchKernelGGL((k_stft<LH, 2, UN>), dim3((unsigned)(ceil_div(ceil_div(n_frames, FftGeom<LH>::Frames), 8) * 8)),   \
-                     dim3(FftGeom<LH>::Threads),                                                                         \
-                     (size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2) +                              \
-                         (size_t)FftGeom<LH>::Threads / kWave * sizeof(double),                                          \
-                     as_stream(stream), x, n, x_stride, n_fft, hop, window, tw.w, tw.post, outf, n_frames, scale, band)
-#define PAR_BAND_LAUNCH(LH)                        \
-  do {                                             \
-    if (x_stride == 1) PAR_BAND_LAUNCH_U(LH, true); \
-    else PAR_BAND_LAUNCH_U(LH, false);              \
-  } while (0)
-  switch (ilog2(H)) {
-    case 3: PAR_BAND_LAUNCH(3); break;
-    case 4: PAR_BAND_LAUNCH(4); break;
-    case 5: PAR_BAND_LAUNCH(5); break;
-    case 6: PAR_BAND_LAUNCH(6); break;
-    case 7: PAR_BAND_LAUNCH(7); break;
-    case 8: PAR_BAND_LAUNCH(8); break;
-    case 9: PAR_BAND_LAUNCH(9); break;
-    case 10: PAR_BAND_LAUNCH(10); break;
-    case 11: PAR_BAND_LAUNCH(11); break;
-    case 12: PAR_BAND_LAUNCH(12); break;
-    case 13: {
-      constexpr int kLds13 = FftGeom<13>::Frames * FftGeom<13>::FrameLds * (int)sizeof(float2) + FftGeom<13>::Threads / kWave * 8;
-      for (const void* fn : {reinterpret_cast<const void*>(&k_stft<13, 2, true>), reinterpret_cast<const void*>(&k_stft<13, 2, false>)}) {
-        const int rc2 = raise_dynamic_lds(fn, kLds13, device);
-        if (rc2 != PAR_OK) return rc2;
-      }
-      PAR_BAND_LAUNCH(13);
-      break;
-    }
-    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_band_db_f32: unsupported size");
-  }
-#undef PAR_BAND_LAUNCH
-#undef PAR_BAND_LAUNCH_U
-  PAR_HIP_CHECK(hipGetLastError());
-  return PAR_OK;
+  return dispatch_logh<3, 13>(ilog2(H), [&](auto lh) {
+    return dispatch_bool(x_stride == 1, [&](auto unit) {
+      using G = FftGeom<decltype(lh)::value>;
+      // beside the frames: the waves' partial sums (frame_lane_sum)
+      return launch_with_lds(k_stft<decltype(lh)::value, 2, decltype(unit)::value>, dim3(G::grid(n_frames)), dim3(G::Threads),
+                             G::FramesLds + (size_t)G::Threads / kWave * sizeof(double), device, as_stream(stream), x, n, x_stride, n_fft,
+                             hop, window, tw.w, tw.post, outf, n_frames, scale, band);
+    });
+  });
 }
 
 // Stereo balance boxes straight from the two channels (k_stft_pan): fac[b], count[b] as par_pan_ratio_f32 gives them on the
@@ -2307,13 +2249,12 @@ int par_stft_pan_ratio_f32(int device, const float* xL, const float* xR, int64_t
   PAR_REQUIRE(n >= 1 && x_stride >= 1 && hop >= 1 && zeropad >= 1 && n_fft >= 2 && n_box >= 1 && n_box <= kPanMaxBoxes, PAR_ERR_ARG,
               "par_stft_pan_ratio_f32: bad sizes");
   PAR_REQUIRE(((uintptr_t)scratch & 15) == 0, PAR_ERR_ARG, "par_stft_pan_ratio_f32: scratch is not 16-byte aligned");
-  const int64_t M64 = (int64_t)n_fft * zeropad;
-  PAR_REQUIRE(M64 >= 16 && M64 <= 16384 && (M64 & (M64 - 1)) == 0 && (n_fft % 2) == 0, PAR_ERR_UNSUPPORTED,
-              "par_stft_pan_ratio_f32: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)M64);
-  const int M = (int)M64, H = M / 2;
+  int rc = require_stft_size("par_stft_pan_ratio_f32", n_fft, zeropad);
+  if (rc != PAR_OK) return rc;
+  const int M = n_fft * zeropad, H = M / 2;
   const int64_t n_frames = par_stft_frames(n, n_fft, hop);
   int64_t n_items = 0;
-  int rc = pan_check_boxes("par_stft_pan_ratio_f32", boxes_host, n_box, H + 1, n_frames, &n_items);
+  rc = pan_check_boxes("par_stft_pan_ratio_f32", boxes_host, n_box, H + 1, n_frames, &n_items);
   if (rc != PAR_OK) return rc;
   PAR_REQUIRE(scratch_bytes >= pan_scratch_bytes(boxes_host, n_box), PAR_ERR_WORKSPACE, "par_stft_pan_ratio_f32: scratch %zu < %zu",
               scratch_bytes, pan_scratch_bytes(boxes_host, n_box));
@@ -2328,43 +2269,18 @@ int par_stft_pan_ratio_f32(int device, const float* xL, const float* xR, int64_t
   // an interleaved stereo pair: both channels of a sample in one aligned 8-byte load
   const bool pair = xR == xL + 1 && x_stride == 2 && ((uintptr_t)xL & 7) == 0;
   launch_pan_offsets(boxes, n_box, scratch, s);
-#define PAR_PAN_LDS(LH) ((size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2) + (size_t)FftGeom<LH>::Threads / kWave * 16)
-#define PAR_PAN_LAUNCH_P(LH, PR)                                                                                               \
-  hipLaunchKernelGGL((k_stft_pan<LH, PR>), dim3((unsigned)(ceil_div(ceil_div(n_items, FftGeom<LH>::Frames), 8) * 8)),            \
-                     dim3(FftGeom<LH>::Threads), PAR_PAN_LDS(LH), s, xL, xR, n, x_stride, n_fft, hop, window, tw.w, tw.post, boxes, \
-                     n_box, offs, part, n_items, scale)
-#define PAR_PAN_LAUNCH(LH)                 \
-  do {                                     \
-    if (pair) PAR_PAN_LAUNCH_P(LH, true);  \
-    else PAR_PAN_LAUNCH_P(LH, false);      \
-  } while (0)
   if (n_items > 0) {
-    switch (ilog2(H)) {
-      case 3: PAR_PAN_LAUNCH(3); break;
-      case 4: PAR_PAN_LAUNCH(4); break;
-      case 5: PAR_PAN_LAUNCH(5); break;
-      case 6: PAR_PAN_LAUNCH(6); break;
-      case 7: PAR_PAN_LAUNCH(7); break;
-      case 8: PAR_PAN_LAUNCH(8); break;
-      case 9: PAR_PAN_LAUNCH(9); break;
-      case 10: PAR_PAN_LAUNCH(10); break;
-      case 11: PAR_PAN_LAUNCH(11); break;
-      case 12: PAR_PAN_LAUNCH(12); break;
-      case 13: {
-        // 72 KB of LDS, above a kernel's default 64 KB (as k_stft at this size)
-        for (const void* fn : {reinterpret_cast<const void*>(&k_stft_pan<13, true>), reinterpret_cast<const void*>(&k_stft_pan<13, false>)}) {
-          const int rc2 = raise_dynamic_lds(fn, (int)PAR_PAN_LDS(13), device);
-          if (rc2 != PAR_OK) return rc2;
-        }
-        PAR_PAN_LAUNCH(13);
-        break;
-      }
-      default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_pan_ratio_f32: unsupported size");
-    }
+    rc = dispatch_logh<3, 13>(ilog2(H), [&](auto lh) {
+      return dispatch_bool(pair, [&](auto pr) {
+        using G = FftGeom<decltype(lh)::value>;
+        // beside the frames: the waves' partial sums and counts (frame_lane_sum)
+        return launch_with_lds(k_stft_pan<decltype(lh)::value, decltype(pr)::value>, dim3(G::grid(n_items)), dim3(G::Threads),
+                               G::FramesLds + (size_t)G::Threads / kWave * 16, device, s, xL, xR, n, x_stride, n_fft, hop, window, tw.w,
+                               tw.post, boxes, n_box, offs, part, n_items, scale);
+      });
+    });
+    if (rc != PAR_OK) return rc;
   }
-#undef PAR_PAN_LAUNCH
-#undef PAR_PAN_LAUNCH_P
-#undef PAR_PAN_LDS
   launch_pan_reduce(n_box, scratch, fac, count, s);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
@@ -2372,13 +2288,8 @@ int par_stft_pan_ratio_f32(int device, const float* xL, const float* xR, int64_t
 
 // Time-averaged dB spectra of all channels straight from the samples (k_stft_mean + k_mean_db_reduce): what
 // par_mean_db_frames_f32 sums over the mode-1 spectrogram of each channel, divided by the frame count, without the spectrogram.
-static bool stft_mean_supported(int n_fft, int zeropad) {
-  const int64_t M = (int64_t)n_fft * zeropad;
-  return n_fft >= 2 && zeropad >= 1 && (n_fft % 2) == 0 && M >= 16 && M <= 16384 && (M & (M - 1)) == 0;
-}
-
 size_t par_stft_mean_db_scratch_bytes(int64_t n, int n_fft, int hop, int zeropad, int n_ch) {
-  if (n < 1 || hop < 1 || n_ch < 1 || n_ch > 8 || !stft_mean_supported(n_fft, zeropad)) return 0;
+  if (n < 1 || hop < 1 || n_ch < 1 || n_ch > 8 || !stft_size_supported(n_fft, zeropad)) return 0;
   const int64_t n_frames = par_stft_frames(n, n_fft, hop);
   const int64_t n_runs = par::ceil_div(n_frames, par::mean_run_len(n_frames));
   return (size_t)n_ch * (size_t)n_runs * (size_t)((int64_t)n_fft * zeropad / 2 + 1) * sizeof(double);
@@ -2392,8 +2303,8 @@ int par_stft_mean_db_f32(int device, const float* x, int64_t n, int64_t x_stride
               "par_stft_mean_db_f32: bad sizes (n %lld, n_fft %d, hop %d, zeropad %d, channels %d, stride %lld)", (long long)n, n_fft, hop,
               zeropad, n_ch, (long long)x_stride);
   PAR_REQUIRE(((uintptr_t)scratch & 7) == 0 && ((uintptr_t)mean & 7) == 0, PAR_ERR_ARG, "par_stft_mean_db_f32: mean or scratch is not 8-byte aligned");
-  PAR_REQUIRE(stft_mean_supported(n_fft, zeropad), PAR_ERR_UNSUPPORTED,
-              "par_stft_mean_db_f32: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)n_fft * zeropad);
+  int rc = require_stft_size("par_stft_mean_db_f32", n_fft, zeropad);
+  if (rc != PAR_OK) return rc;
   const size_t need = par_stft_mean_db_scratch_bytes(n, n_fft, hop, zeropad, n_ch);
   PAR_REQUIRE(scratch_bytes >= need, PAR_ERR_WORKSPACE, "par_stft_mean_db_f32: scratch %zu < %zu", scratch_bytes, need);
   const int M = n_fft * zeropad, H = M / 2;
@@ -2401,46 +2312,19 @@ int par_stft_mean_db_f32(int device, const float* x, int64_t n, int64_t x_stride
   const int64_t run = mean_run_len(n_frames), n_runs = ceil_div(n_frames, run);
   PAR_HIP_CHECK(hipSetDevice(device));
   Twiddles tw;
-  int rc = get_twiddles(device, M, &tw);
+  rc = get_twiddles(device, M, &tw);
   if (rc != PAR_OK) return rc;
   hipStream_t s = as_stream(stream);
   const float scale = (float)(1.0 / sqrt((double)n_fft));
   double* part = reinterpret_cast<double*>(scratch);
-#define PAR_MEAN_LDS(LH) ((size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2))
-#define PAR_MEAN_LAUNCH_U(LH, UN)                                                                                              \
-  hipLaunchKernelGGL((k_stft_mean<LH, UN>), dim3((unsigned)(ceil_div(ceil_div(n_runs, FftGeom<LH>::Frames), 8) * 8), (unsigned)n_ch), \
-                     dim3(FftGeom<LH>::Threads), PAR_MEAN_LDS(LH), s, x, n, x_stride, n_fft, hop, window, tw.w, tw.post, part,   \
-                     n_frames, run, n_runs, scale)
-#define PAR_MEAN_LAUNCH(LH)                         \
-  do {                                              \
-    if (x_stride == 1) PAR_MEAN_LAUNCH_U(LH, true); \
-    else PAR_MEAN_LAUNCH_U(LH, false);              \
-  } while (0)
-  switch (ilog2(H)) {
-    case 3: PAR_MEAN_LAUNCH(3); break;
-    case 4: PAR_MEAN_LAUNCH(4); break;
-    case 5: PAR_MEAN_LAUNCH(5); break;
-    case 6: PAR_MEAN_LAUNCH(6); break;
-    case 7: PAR_MEAN_LAUNCH(7); break;
-    case 8: PAR_MEAN_LAUNCH(8); break;
-    case 9: PAR_MEAN_LAUNCH(9); break;
-    case 10: PAR_MEAN_LAUNCH(10); break;
-    case 11: PAR_MEAN_LAUNCH(11); break;
-    case 12: PAR_MEAN_LAUNCH(12); break;
-    case 13: {
-      // 72 KB of LDS, above a kernel's default 64 KB (as k_stft at this size)
-      for (const void* fn : {reinterpret_cast<const void*>(&k_stft_mean<13, true>), reinterpret_cast<const void*>(&k_stft_mean<13, false>)}) {
-        const int rc2 = raise_dynamic_lds(fn, (int)PAR_MEAN_LDS(13), device);
-        if (rc2 != PAR_OK) return rc2;
-      }
-      PAR_MEAN_LAUNCH(13);
-      break;
-    }
-    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_mean_db_f32: unsupported size");
-  }
-#undef PAR_MEAN_LAUNCH
-#undef PAR_MEAN_LAUNCH_U
-#undef PAR_MEAN_LDS
+  rc = dispatch_logh<3, 13>(ilog2(H), [&](auto lh) {
+    return dispatch_bool(x_stride == 1, [&](auto unit) {
+      using G = FftGeom<decltype(lh)::value>;
+      return launch_with_lds(k_stft_mean<decltype(lh)::value, decltype(unit)::value>, dim3(G::grid(n_runs), (unsigned)n_ch), dim3(G::Threads),
+                             G::FramesLds, device, s, x, n, x_stride, n_fft, hop, window, tw.w, tw.post, part, n_frames, run, n_runs, scale);
+    });
+  });
+  if (rc != PAR_OK) return rc;
   const int bins = H + 1;
   hipLaunchKernelGGL(k_mean_db_reduce, dim3((unsigned)ceil_div(bins, 256), (unsigned)n_ch), dim3(256), 0, s, part, n_runs, bins, n_frames, mean);
   PAR_HIP_CHECK(hipGetLastError());
@@ -2461,13 +2345,13 @@ int par_stft_track_peak_f64(int device, const float* x, int64_t n, int64_t x_str
               PAR_ERR_ARG, "par_stft_track_peak_f64: frames [%lld, %lld + %lld) of %lld", (long long)frame_0, (long long)frame_0,
               (long long)count, (long long)par_stft_frames(n, n_fft, hop));
   PAR_REQUIRE((mode == 0 || mode == 1) && (db == 0 || db == 1), PAR_ERR_ARG, "par_stft_track_peak_f64: mode and db must be 0 or 1");
-  PAR_REQUIRE(stft_mean_supported(n_fft, zeropad), PAR_ERR_UNSUPPORTED,
-              "par_stft_track_peak_f64: n_fft*zeropad=%lld is not a power of two in [16, 16384]", (long long)n_fft * zeropad);
+  int rc = require_stft_size("par_stft_track_peak_f64", n_fft, zeropad);
+  if (rc != PAR_OK) return rc;
   if (count == 0) return PAR_OK;
   const int M = n_fft * zeropad, H = M / 2;
   PAR_HIP_CHECK(hipSetDevice(device));
   Twiddles tw;
-  int rc = get_twiddles(device, M, &tw);
+  rc = get_twiddles(device, M, &tw);
   if (rc != PAR_OK) return rc;
   hipStream_t s = as_stream(stream);
   PAR_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), s));
@@ -2477,45 +2361,17 @@ int par_stft_track_peak_f64(int device, const float* x, int64_t n, int64_t x_str
     PAR_HIP_CHECK(hipStreamSynchronize(s));
   }
   const float scale = (float)(1.0 / sqrt((double)n_fft));
-  // the frames, then per frame 4 ints of band and one (value, bin) pair per wave of the frame
-#define PAR_PEAK_LDS(LH)                                                     \
-  ((size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2) +    \
-   (size_t)FftGeom<LH>::Frames * (4 + 2 * (FftGeom<LH>::T > kWave ? FftGeom<LH>::T / kWave : 1)) * sizeof(int))
-#define PAR_PEAK_LAUNCH_U(LH, UN)                                                                                              \
-  hipLaunchKernelGGL((k_stft_peak<LH, UN>), dim3((unsigned)(ceil_div(ceil_div(count, FftGeom<LH>::Frames), 8) * 8)),            \
-                     dim3(FftGeom<LH>::Threads), PAR_PEAK_LDS(LH), s, x, n, x_stride, n_fft, hop, window, tw.w, tw.post, frame_0, \
-                     count, freqs, centre, sr, tolerance_oct, mode, db, status, scale)
-#define PAR_PEAK_LAUNCH(LH)                         \
-  do {                                              \
-    if (x_stride == 1) PAR_PEAK_LAUNCH_U(LH, true); \
-    else PAR_PEAK_LAUNCH_U(LH, false);              \
-  } while (0)
-  switch (ilog2(H)) {
-    case 3: PAR_PEAK_LAUNCH(3); break;
-    case 4: PAR_PEAK_LAUNCH(4); break;
-    case 5: PAR_PEAK_LAUNCH(5); break;
-    case 6: PAR_PEAK_LAUNCH(6); break;
-    case 7: PAR_PEAK_LAUNCH(7); break;
-    case 8: PAR_PEAK_LAUNCH(8); break;
-    case 9: PAR_PEAK_LAUNCH(9); break;
-    case 10: PAR_PEAK_LAUNCH(10); break;
-    case 11: PAR_PEAK_LAUNCH(11); break;
-    case 12: PAR_PEAK_LAUNCH(12); break;
-    case 13: {
-      // 72 KB of LDS, above a kernel's default 64 KB (as k_stft at this size)
-      for (const void* fn : {reinterpret_cast<const void*>(&k_stft_peak<13, true>), reinterpret_cast<const void*>(&k_stft_peak<13, false>)}) {
-        const int rc2 = raise_dynamic_lds(fn, (int)PAR_PEAK_LDS(13), device);
-        if (rc2 != PAR_OK) return rc2;
-      }
-      PAR_PEAK_LAUNCH(13);
-      break;
-    }
-    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_stft_track_peak_f64: unsupported size");
-  }
-#undef PAR_PEAK_LAUNCH
-#undef PAR_PEAK_LAUNCH_U
-#undef PAR_PEAK_LDS
-  PAR_HIP_CHECK(hipGetLastError());
+  rc = dispatch_logh<3, 13>(ilog2(H), [&](auto lh) {
+    return dispatch_bool(x_stride == 1, [&](auto unit) {
+      using G = FftGeom<decltype(lh)::value>;
+      // the frames, then per frame 4 ints of band and one (value, bin) pair per wave of the frame
+      return launch_with_lds(k_stft_peak<decltype(lh)::value, decltype(unit)::value>, dim3(G::grid(count)), dim3(G::Threads),
+                             G::FramesLds + (size_t)G::Frames * (4 + 2 * (G::T > kWave ? G::T / kWave : 1)) * sizeof(int), device, s, x, n,
+                             x_stride, n_fft, hop, window, tw.w, tw.post, frame_0, count, freqs, centre, sr, tolerance_oct, mode, db,
+                             status, scale);
+    });
+  });
+  if (rc != PAR_OK) return rc;
   return check_empty(status, s, "par_stft_track_peak_f64");
 }
 
@@ -2939,49 +2795,20 @@ int par_istft_f32(int device, const float* spec, int64_t n_frames, int n_fft, in
   if (istft_is_fused(n_fft, hop)) {
     if (y_len == 0) return PAR_OK;
     const int s = (n_fft + hop - 1) / hop;
-#define PAR_ISTFT_FUSED(LH)                                                                                             \
-  {                                                                                                                     \
-    const int64_t out_len = (int64_t)(FftGeom<LH>::Frames * s - s + 1) * hop;                                             \
-    hipLaunchKernelGGL(k_istft_fused<LH>, dim3((unsigned)ceil_div(y_len + skip, out_len)), dim3(FftGeom<LH>::Threads),    \
-                       istft_fused_lds<LH>(hop), as_stream(stream), sp2, n_frames, hop, s, window, tw.w, tw.post, y,     \
-                       y_len, skip, scale);                                                                              \
+    return dispatch_logh<3, 12>(ilog2(H), [&](auto lh) {
+      constexpr int LH = decltype(lh)::value;
+      const int64_t out_len = (int64_t)(FftGeom<LH>::Frames * s - s + 1) * hop;
+      return launch_with_lds(k_istft_fused<LH>, dim3((unsigned)ceil_div(y_len + skip, out_len)), dim3(FftGeom<LH>::Threads),
+                             istft_fused_lds<LH>(hop), device, as_stream(stream), sp2, n_frames, hop, s, window, tw.w, tw.post, y, y_len,
+                             skip, scale);
+    });
   }
-    switch (ilog2(H)) {
-      case 3: PAR_ISTFT_FUSED(3); break;
-      case 4: PAR_ISTFT_FUSED(4); break;
-      case 5: PAR_ISTFT_FUSED(5); break;
-      case 6: PAR_ISTFT_FUSED(6); break;
-      case 7: PAR_ISTFT_FUSED(7); break;
-      case 8: PAR_ISTFT_FUSED(8); break;
-      case 9: PAR_ISTFT_FUSED(9); break;
-      case 10: PAR_ISTFT_FUSED(10); break;
-      case 11: PAR_ISTFT_FUSED(11); break;
-      case 12: PAR_ISTFT_FUSED(12); break;
-      default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_istft_f32: unsupported size");
-    }
-#undef PAR_ISTFT_FUSED
-    PAR_HIP_CHECK(hipGetLastError());
-    return PAR_OK;
-  }
-#define PAR_ISTFT_LAUNCH(LH)                                                                                            \
-  hipLaunchKernelGGL(k_istft_frames<LH>, dim3((unsigned)ceil_div(n_frames, FftGeom<LH>::Frames)),                         \
-                     dim3(FftGeom<LH>::Threads), (size_t)FftGeom<LH>::Frames * FftGeom<LH>::FrameLds * sizeof(float2),      \
-                     as_stream(stream), sp2, n_frames, window, tw.w, tw.post, frames, scale)
-  switch (ilog2(H)) {
-    case 3: PAR_ISTFT_LAUNCH(3); break;
-    case 4: PAR_ISTFT_LAUNCH(4); break;
-    case 5: PAR_ISTFT_LAUNCH(5); break;
-    case 6: PAR_ISTFT_LAUNCH(6); break;
-    case 7: PAR_ISTFT_LAUNCH(7); break;
-    case 8: PAR_ISTFT_LAUNCH(8); break;
-    case 9: PAR_ISTFT_LAUNCH(9); break;
-    case 10: PAR_ISTFT_LAUNCH(10); break;
-    case 11: PAR_ISTFT_LAUNCH(11); break;
-    case 12: PAR_ISTFT_LAUNCH(12); break;
-    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_istft_f32: unsupported size");
-  }
-#undef PAR_ISTFT_LAUNCH
-  PAR_HIP_CHECK(hipGetLastError());
+  rc = dispatch_logh<3, 12>(ilog2(H), [&](auto lh) {
+    using G = FftGeom<decltype(lh)::value>;
+    return launch_with_lds(k_istft_frames<decltype(lh)::value>, dim3((unsigned)ceil_div(n_frames, G::Frames)), dim3(G::Threads), G::FramesLds,
+                           device, as_stream(stream), sp2, n_frames, window, tw.w, tw.post, frames, scale);
+  });
+  if (rc != PAR_OK) return rc;
   if (y_len > 0) {
     hipLaunchKernelGGL(k_istft_ola, dim3((unsigned)ceil_div(y_len, 256)), dim3(256), 0, as_stream(stream), frames,
                        n_frames, n_fft, hop, window, y, y_len, skip);
@@ -3037,34 +2864,29 @@ extern "C" int par_gate_spectrum_f32(int device, float* spec, int64_t n_frames, 
 }
 
 static int gate_stft_sizes(int64_t n, int n_fft, int hop, int64_t* n_frames_i, int* s, int* rounds, int* ring, int64_t* runs,
-                           size_t* lds) {
+                           size_t* lds, int* frames_per_round) {
   using namespace par;
   if (n < 1 || hop < 1 || hop > n_fft || n_fft < 16 || n_fft > 8192 || (n_fft & (n_fft - 1))) return PAR_ERR_UNSUPPORTED;
   const int64_t frames = par_stft_frames(n + n_fft / 2, n_fft, hop);                    // STFT of fix_length(x, n + n_fft/2)
   const int64_t want = ceil_div(n + n_fft, hop);                                        // istft(length=n) keeps these
   *n_frames_i = frames < want ? frames : want;
   *s = (int)ceil_div(n_fft, hop);
-#define PAR_GATE_GEOM(LH)                                                          \
-  case LH:                                                                         \
-    *rounds = GateGeom<LH>::rounds(*s);                                            \
-    *ring = GateGeom<LH>::ring(hop);                                               \
-    *lds = GateGeom<LH>::lds(hop);                                                 \
-    *runs = ceil_div(n + n_fft / 2, (int64_t)(FftGeom<LH>::Frames * *rounds - (*s - 1)) * hop); \
+  return dispatch_logh<3, 12>(ilog2(n_fft / 2), [&](auto lh) {
+    using GG = GateGeom<decltype(lh)::value>;
+    *frames_per_round = GG::G::Frames;
+    *rounds = GG::rounds(*s);
+    *ring = GG::ring(hop);
+    *lds = GG::lds(hop);
+    *runs = ceil_div(n + n_fft / 2, (int64_t)(GG::G::Frames * *rounds - (*s - 1)) * hop);
     return (*lds <= 160 * 1024) ? PAR_OK : PAR_ERR_UNSUPPORTED;
-  switch (ilog2(n_fft / 2)) {
-    PAR_GATE_GEOM(3) PAR_GATE_GEOM(4) PAR_GATE_GEOM(5) PAR_GATE_GEOM(6) PAR_GATE_GEOM(7)
-    PAR_GATE_GEOM(8) PAR_GATE_GEOM(9) PAR_GATE_GEOM(10) PAR_GATE_GEOM(11) PAR_GATE_GEOM(12)
-  }
-#undef PAR_GATE_GEOM
-  return PAR_ERR_UNSUPPORTED;
+  });
 }
 
 extern "C" int64_t par_gate_stft_transformed_frames(int64_t n, int n_fft, int hop) {
   int64_t nfi = 0, runs = 0;
-  int s = 0, rounds = 0, ring = 0;
+  int s = 0, rounds = 0, ring = 0, frames_per_round = 0;
   size_t lds = 0;
-  if (gate_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds) != PAR_OK) return 0;
-  const int frames_per_round = (int)((n_fft / 2) / 8 > 256 ? 1 : 256 / ((n_fft / 2) / 8));
+  if (gate_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds, &frames_per_round) != PAR_OK) return 0;
   // every run but the last transforms all its rounds; the last stops once its rounds reach the end of the output
   const int64_t out = (int64_t)frames_per_round * rounds - (s - 1);
   int64_t total = 0;
@@ -3086,9 +2908,9 @@ extern "C" int par_gate_stft_f32(int device, const float* x, int64_t n, int64_t 
               "par_gate_stft_f32: bad sizes (n %lld, channels %d, strides %lld / %lld, hop %d)", (long long)n, n_ch,
               (long long)x_stride, (long long)y_stride, hop);
   int64_t nfi = 0, runs = 0;
-  int s = 0, rounds = 0, ring = 0;
+  int s = 0, rounds = 0, ring = 0, frames_per_round = 0;
   size_t lds = 0;
-  PAR_REQUIRE(gate_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds) == PAR_OK, PAR_ERR_UNSUPPORTED,
+  PAR_REQUIRE(gate_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds, &frames_per_round) == PAR_OK, PAR_ERR_UNSUPPORTED,
               "par_gate_stft_f32: n_fft=%d hop=%d (a power of two in [16, 8192], 1 <= hop <= n_fft)", n_fft, hop);
   PAR_REQUIRE(runs <= 0x7fffffff, PAR_ERR_UNSUPPORTED, "par_gate_stft_f32: signal too long");
   PAR_HIP_CHECK(hipSetDevice(device));
@@ -3097,21 +2919,9 @@ extern "C" int par_gate_stft_f32(int device, const float* x, int64_t n, int64_t 
   if (rc != PAR_OK) return rc;
   const float fscale = (float)(1.0 / sqrt((double)n_fft));
   const float iscale = (float)(sqrt((double)n_fft) / (double)(n_fft / 2));
-#define PAR_GATE_LAUNCH(LH)                                                                                              \
-  case LH: {                                                                                                             \
-    rc = raise_dynamic_lds(reinterpret_cast<const void*>(&k_gate_stft<LH>), (int)lds, device);                           \
-    if (rc != PAR_OK) return rc;                                                                                         \
-    hipLaunchKernelGGL(k_gate_stft<LH>, dim3((unsigned)runs, (unsigned)n_ch), dim3(FftGeom<LH>::Threads), lds,           \
-                       as_stream(stream), x, n, x_stride, hop, s, rounds, ring, window, tw.w, tw.post, cutoff, low, y,   \
-                       y_stride, nfi, fscale, iscale);                                                                   \
-    break;                                                                                                               \
-  }
-  switch (ilog2(n_fft / 2)) {
-    PAR_GATE_LAUNCH(3) PAR_GATE_LAUNCH(4) PAR_GATE_LAUNCH(5) PAR_GATE_LAUNCH(6) PAR_GATE_LAUNCH(7)
-    PAR_GATE_LAUNCH(8) PAR_GATE_LAUNCH(9) PAR_GATE_LAUNCH(10) PAR_GATE_LAUNCH(11) PAR_GATE_LAUNCH(12)
-    default: PAR_REQUIRE(false, PAR_ERR_UNSUPPORTED, "par_gate_stft_f32: unsupported size");
-  }
-#undef PAR_GATE_LAUNCH
-  PAR_HIP_CHECK(hipGetLastError());
-  return PAR_OK;
+  return dispatch_logh<3, 12>(ilog2(n_fft / 2), [&](auto lh) {
+    return launch_with_lds(k_gate_stft<decltype(lh)::value>, dim3((unsigned)runs, (unsigned)n_ch), dim3(FftGeom<decltype(lh)::value>::Threads),
+                           lds, device, as_stream(stream), x, n, x_stride, hop, s, rounds, ring, window, tw.w, tw.post, cutoff, low, y,
+                           y_stride, nfi, fscale, iscale);
+  });
 }

@@ -70,6 +70,9 @@ def kernel_cases():
         for nf in counts:
             hop = M // 2
             c.append(KCase(M, 1, hop, n_for(nf, hop), 1, 1, "noise"))
+    # the lane counts between those (T = 2, 8, 16, 512) at hop n_fft / 4: one frame more than the frame slots of a workgroup
+    for M, slots in ((32, 128), (128, 32), (256, 16), (8192, 1)):
+        c.append(KCase(M, 1, M // 4, n_for(slots + 1, M // 4), 1, 1, "noise"))
     # more than one workgroup at every slot count, a run longer than 16 (n_frames > 8192 -> 17), hop 1
     c += [KCase(16, 1, 1, 4100, 1, 1, "noise"), KCase(16, 1, 1, 8300, 2, 2, "noise"), KCase(512, 1, 256, n_for(147, 256), 2, 2, "noise"),
           KCase(1024, 1, 512, n_for(100, 512), 1, 2, "noise"), KCase(2048, 1, 1024, n_for(70, 1024), 2, 3, "noise")]

@@ -149,7 +149,10 @@ def is_denormal(a):
 
 
 # ---- fused gate: signals ---------------------------------------------------------------------------------------------------------
-FUSED_SETTINGS = ((64, 16, 3001), (512, 128, 9001), (2048, 512, 20001), (8192, 2048, 40001))      # (n_fft, hop, n)
+FUSED_SETTINGS = ((64, 16, 3001), (512, 128, 9001), (2048, 512, 20001), (8192, 2048, 40001),      # (n_fft, hop, n)
+                  # 2, 8 and 16 lanes per frame at hop n_fft / 4, one frame more than a workgroup's round holds (128, 32, 16):
+                  # (n + n_fft / 2) // hop + 1 frames
+                  (32, 8, 1008), (128, 32, 960), (256, 64, 896))
 
 
 def fused_signal(n, seed=0):

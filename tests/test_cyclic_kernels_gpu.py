@@ -66,6 +66,9 @@ def cases():
         n = hop * (F + 4) + 7
         for count, frame_0 in sorted({(1, 0), (max(1, F - 1), 2), (F, 0), (F + 1, 1)}):
             add(f"M{M}_zp{zp}_c{count}_f{frame_0}", n_fft, zp, hop, n, frame_0=frame_0, count=count, tol=0.31 if M > 16 else 0.05)
+    # the lane counts between those (T = 2, 8, 16, 512): one frame more than a workgroup holds, both ends reflecting
+    for M in (32, 128, 256, 8192):
+        add(f"M{M}_group_plus_1", M, 1, M // 4, (M // 4) * frames_per_group(M) + 1)
     add("hop1", 64, 1, 1, 300)
     add("odd_hop", 1024, 1, 341, 9000)
     add("hop_above_n_fft", 256, 2, 300, 3000)

@@ -235,6 +235,7 @@ def edge_cells(n_fft, zp, hop, n, group):
 @pytest.mark.parametrize("n_fft,zp,hop,n,group", [
     (16, 1, 4, 1100, 256), (64, 1, 16, 1200, 64), (1024, 1, 256, 3000, 4), (2048, 1, 512, 5000, 2), (16384, 1, 4096, 40000, 1),
     (512, 2, 128, 2000, 4),
+    (32, 1, 8, 1025, 128), (128, 1, 32, 1025, 32), (8192, 1, 2048, 2049, 1),     # 2, 8 and 512 lanes per frame: group + 1 frames at hop n_fft / 4
     (256, 1, 256, 3000, 8),            # hop == n_fft
     (64, 1, 1, 200, 64),               # hop == 1
     (1024, 1, 256, 300, 4)])           # a signal shorter than n_fft / 2: every frame reflects, more than once
