@@ -388,7 +388,10 @@ int par_track_corr_f64(int device, const float* mag, int64_t n_frames, int bins,
  *                       multiplies a and b in place): the peak of the 'same' correlation is located by the transform,
  *                       the lags around it are re-evaluated as float64 dot products and parabolic() (:42-46) runs on
  *                       those; *delay = peak - na//2 (host), *corr = its height.  A peak on the last lag is the
- *                       reference's IndexError: PAR_ERR_INDEX.  Synchronises.
+ *                       reference's IndexError: PAR_ERR_INDEX.  The call is par_find_delay_batch_f64's work on one row,
+ *                       by the same kernels, decided on the device (the peak is sought in the float64 correlation
+ *                       array, the same doubles a batch row reads out of its transform); it synchronises once, to
+ *                       copy delay, corr and the row's status to the host.
  *                       Rival peaks: every local maximum of the transform's output within kXcRivalTol = 4.0e-6 of its
  *                       top, more than two lags from it, is re-evaluated exactly and the exact values decide (lowest
  *                       lag on a tie).  The exact argmax is certain to be listed while twice the transform's worst
@@ -412,12 +415,12 @@ int par_find_delay_f64(int device, const double* a, int64_t na, const double* b,
  *                       0 = ok, 1 = the peak sits on lag na - 1 (the reference's IndexError in parabolic()): delay and
  *                       corr of THAT row are NaN, every other row is computed.  A row of zeros has norm 0: delay and corr
  *                       are NaN with status 0, as the reference's division carries it.
- *                       The work per window is par_find_delay_f64's -- norms, one packed float32 transform pair, first
- *                       argmax, rivals within kXcRivalTol re-decided exactly (64 or more: the transform's top stands),
- *                       exact values at peak-3 .. peak+3, numpy's f[-1] wrap at peak 0, parabolic() -- decided on the
- *                       device: nothing is copied to the host and the call does not synchronise (a device's first
- *                       call of a transform size uploads its twiddles).  Every value that enters (delay, corr) is the
- *                       float64 sum par_find_delay_f64 forms, in its order: row by row the results are its results.
+ *                       The work per window -- norms, one packed float32 transform pair, first argmax, rivals within
+ *                       kXcRivalTol re-decided exactly (64 or more: the transform's top stands), exact values at
+ *                       peak-3 .. peak+3, numpy's f[-1] wrap at peak 0, parabolic() -- is decided on the device:
+ *                       nothing is copied to the host and the call does not synchronise (a device's first call of a
+ *                       transform size uploads its twiddles).  par_find_delay_f64 is this call's n_win = 1 through the
+ *                       same kernels: a row's results do not depend on its neighbours, its pitch, n_win or the entry.
  *                       na + nb - 1 <= 2^20 (one transform per window), else PAR_ERR_UNSUPPORTED: loop over
  *                       par_find_delay_f64.  na < 3, nb < 1, n_win < 0, a pitch below its length, a null pointer:
  *                       PAR_ERR_ARG before any device call.  n_win == 0: PAR_OK, nothing done.

@@ -1,7 +1,9 @@
 """Correlation helpers with the call contracts of the reference's util/correlation.py (xcorr :6-13,
 find_delay :16-39, parabolic :42-46), on the device: `par_xcorr_f64` / `par_find_delay_f64` (csrc/stft.hip) run the
 correlation through one complex four-step FFT of a/|a| + i b/|b|; find_delay re-evaluates the lags around the peak as
-float64 dot products before the parabolic refinement, so the delay the tape-sync tool reads is exact.
+float64 dot products before the parabolic refinement, so the delay the tape-sync tool reads is exact.  The delay search
+is written once: `par_find_delay_batch_f64` decides W pairs of rows on the device, `par_find_delay_f64` is its W = 1
+through the same kernels and waits once, for delay, corr and the row's status (the reference's IndexError).
 """
 import ctypes
 import logging

@@ -1273,23 +1273,11 @@ __global__ __launch_bounds__(256) void k_huge_out(const float2* __restrict__ Zr,
 // (tests/test_xcorr_gpu.py, unequal levels).  The float32 transform places the peak (error ~1e-6 of it); find_delay
 // then re-evaluates the few lags around it as float64 dot products, so the parabola through the peak -- the delay
 // the tape-sync tool uses -- is exact.
-__global__ __launch_bounds__(256) void k_xc_pack(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
-                                                 int64_t nb, const double* __restrict__ norms, float2* __restrict__ Z, int64_t N) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  Z[i] = make_float2(i < na ? (float)(a[i] / norms[0]) : 0.0f, i < nb ? (float)(b[i] / norms[1]) : 0.0f);
-}
-// conj(A_k conj(B_k)) for the second (forward) transform
-__global__ __launch_bounds__(256) void k_xc_cross(const float2* __restrict__ Z, float2* __restrict__ C, int64_t N) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= N) return;
-  const float2 zk = Z[k], zc = cconj(Z[(N - k) & (N - 1)]);
-  const float2 A = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
-  const float2 d = csub(zk, zc);                            // 2i B_k  ->  B_k = (d.y, -d.x)/2
-  const float2 B = make_float2(0.5f * d.y, -0.5f * d.x);
-  const float2 c = cmul(A, cconj(B));
-  C[k] = cconj(c);
-}
+// ONE family of kernels (k_xcb_*) serves a batch of W pairs of rows of one shape (pytapesynch_gui.py:210-238, the azimuth
+// mode) and the single pair, which is the batch of one: every rule of the search -- the first maximum, the rival list, the
+// plateau, the tie, the best of five, the f[-1] wrap, the last-lag status, the parabola -- is written once, on the device,
+// and no value travels to the host between the stages.  Only k_xc_unpack / k_xc_unpack_acc are the single pair's own: the
+// float64 'full' array is par_xcorr_f64's product, the sectioned form's accumulator and what the single pair's peak stage scans.
 // full[j] = circ[(j - (nb-1)) mod N] / N, j = 0 .. na + nb - 2 (the signals went in normalised)
 __global__ __launch_bounds__(256) void k_xc_unpack(const float2* __restrict__ Y, int64_t N, int64_t nb, int64_t n_full,
                                                    double* __restrict__ full) {
@@ -1304,8 +1292,7 @@ __global__ __launch_bounds__(256) void k_xc_unpack_acc(const float2* __restrict_
   if (j >= n_local) return;
   full[j] += (double)Y[(j - (nbq - 1)) & (N - 1)].x / (double)N;
 }
-// |v| in float64 by one 1024-thread workgroup (valid in thread 0): THE summation order of the norm, shared by the single
-// and the batched delay search so that both divide by the same bits
+// |v| in float64 by one 1024-thread workgroup (valid in thread 0): THE summation order of the norm
 __device__ inline double xc_norm_1024(const double* __restrict__ v, int64_t n, double* part /* LDS [16] */) {
   double acc = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 1024) acc += v[i] * v[i];
@@ -1320,71 +1307,13 @@ __device__ inline double xc_norm_1024(const double* __restrict__ v, int64_t n, d
   }
   return t;
 }
-// norms[0] = |a|, norms[1] = |b| (float64, one workgroup each)
-__global__ __launch_bounds__(1024) void k_xc_norms(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
-                                                   int64_t nb, double* __restrict__ norms) {
-  __shared__ double part[16];
-  const double t = xc_norm_1024(blockIdx.x ? b : a, blockIdx.x ? nb : na, part);
-  if (threadIdx.x == 0) norms[blockIdx.x] = t;
-}
-// first index of the maximum of v[lo .. lo+n) (|v| when ignore_phase), one workgroup
-__global__ __launch_bounds__(1024) void k_xc_argmax(const double* __restrict__ v, int64_t n, int use_abs, long long* __restrict__ arg) {
-  __shared__ double bv[1024];
-  __shared__ long long bi[1024];
-  double best = -INFINITY;
-  long long at = 0;
-  for (int64_t i = threadIdx.x; i < n; i += 1024) {
-    const double x = use_abs ? fabs(v[i]) : v[i];
-    if (x > best) {
-      best = x;
-      at = i;
-    }
-  }
-  bv[threadIdx.x] = best;
-  bi[threadIdx.x] = at;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      const double x = bv[threadIdx.x + o];
-      const long long j = bi[threadIdx.x + o];
-      if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && j < bi[threadIdx.x])) {
-        bv[threadIdx.x] = x;
-        bi[threadIdx.x] = j;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *arg = bi[0];
-}
 constexpr int kXcCand = 64;                        // rival peaks find_delay re-evaluates exactly
 // Listing tolerance: a rival is listed when the transform puts it within kXcRivalTol of the transform's top.  With e the
 // transform's worst error, a rival whose exact value reaches the exact top reads at least top - 2e, so 2e <= kXcRivalTol
 // lists it for certain (include/par_hip.h; measured per transform size in tests/test_xcorr_gpu.py, NOTES.md "Correlation").
 constexpr double kXcRivalTol = 4.0e-6;
-// Rival peaks: the float32 transform finds the peak to ~1e-6 of its height; a periodic tone, or the +/- lobes
-// under ignore_phase, can put another local maximum within that distance of the top more than two lags away, and the
-// reference's float64 argmax may pick that one.  Every local maximum (of |v| under use_abs) within `tol` of the
-// transform's top, more than two lags from it, is listed (up to kXcCand of them) for exact re-evaluation.
-__global__ __launch_bounds__(1024) void k_xc_candidates(const double* __restrict__ v, int64_t n, int use_abs,
-                                                        const long long* __restrict__ arg, double tol,
-                                                        long long* __restrict__ cand, int* __restrict__ n_cand) {
-  const long long top = *arg;
-  const double m = use_abs ? fabs(v[top]) : v[top];
-  for (int64_t i = threadIdx.x; i < n; i += 1024) {
-    if (i >= top - 2 && i <= top + 2) continue;
-    const double x = use_abs ? fabs(v[i]) : v[i];
-    if (!(x >= m - tol)) continue;
-    const double xl = i > 0 ? (use_abs ? fabs(v[i - 1]) : v[i - 1]) : -INFINITY;
-    const double xr = i + 1 < n ? (use_abs ? fabs(v[i + 1]) : v[i + 1]) : -INFINITY;
-    if (x >= xl && x >= xr) {
-      const int slot = atomicAdd(n_cand, 1);
-      if (slot < kXcCand) cand[slot] = i;
-    }
-  }
-}
 // exact 'same' correlation value at lag j by one 256-thread workgroup (valid in thread 0), float64:
-// same[j] = sum_t a[t + j + (nb-1)//2 - (nb-1)] b[t] / (|a| |b|).  THE summation order of every value that enters a delay,
-// shared by the single and the batched search.
+// same[j] = sum_t a[t + j + (nb-1)//2 - (nb-1)] b[t] / (|a| |b|).  THE summation order of every value that enters a delay.
 __device__ inline double xc_exact_256(const double* __restrict__ a, int64_t na, const double* __restrict__ b, int64_t nb,
                                       const double* __restrict__ norms, int64_t j, double* part /* LDS [4] */) {
   double acc = 0.0;
@@ -1401,27 +1330,10 @@ __device__ inline double xc_exact_256(const double* __restrict__ a, int64_t na, 
   __syncthreads();
   return threadIdx.x == 0 ? (part[0] + part[1] + part[2] + part[3]) / (norms[0] * norms[1]) : 0.0;
 }
-// exact 'same' correlation value at every listed lag (one workgroup per entry, float64)
-__global__ __launch_bounds__(256) void k_xc_exact_list(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
-                                                       int64_t nb, const double* __restrict__ norms,
-                                                       const long long* __restrict__ list, double* __restrict__ vals) {
-  __shared__ double part[4];
-  const double v = xc_exact_256(a, na, b, nb, norms, list[blockIdx.x], part);
-  if (threadIdx.x == 0) vals[blockIdx.x] = v;
-}
-// exact 'same' correlation values at lags c0 .. c0+count-1 (one workgroup per lag, float64)
-__global__ __launch_bounds__(256) void k_xc_exact(const double* __restrict__ a, int64_t na, const double* __restrict__ b,
-                                                  int64_t nb, const double* __restrict__ norms, const long long* __restrict__ arg,
-                                                  int64_t rel0, double* __restrict__ vals) {
-  __shared__ double part[4];
-  const double v = xc_exact_256(a, na, b, nb, norms, *arg + rel0 + blockIdx.x, part);
-  if (threadIdx.x == 0) vals[blockIdx.x] = v;
-}
 
-// ---- X2 batch: find_delay for n_win pairs of rows of one shape (pytapesynch_gui.py:210-238, the azimuth mode) ----------
-// The work per window is par_find_delay_f64's, decided on the device: no value travels to the host between the stages.
-// Per window w the tables in scratch are XcbRow (norms, the transform's top, the rival list and its exact values, the
-// seven exact values around the peak and the f[-1] wrap).
+// Per row w (a window of the batch; the single pair is row 0) the tables in scratch are XcbRow: norms, the transform's top,
+// the rival list and its exact values, the seven exact values around the peak and the f[-1] wrap.  In every kernel below
+// the grid's y extent (or, one thread or workgroup per row, its x extent) runs over the rows.
 struct XcbRow {
   double norms[2];
   long long arg;
@@ -1438,6 +1350,7 @@ __global__ __launch_bounds__(256) void k_xcb_window(double* __restrict__ a, int6
   if (win_a && i < na) a[w * a_pitch + i] *= win_a[i];
   if (win_b && i < nb) b[w * b_pitch + i] *= win_b[i];
 }
+// norms[0] = |a|, norms[1] = |b| of every row (float64, one workgroup each)
 __global__ __launch_bounds__(1024) void k_xcb_norms(const double* __restrict__ a, int64_t a_pitch, int64_t na,
                                                     const double* __restrict__ b, int64_t b_pitch, int64_t nb,
                                                     XcbRow* __restrict__ rows) {
@@ -1446,6 +1359,8 @@ __global__ __launch_bounds__(1024) void k_xcb_norms(const double* __restrict__ a
   const double t = xc_norm_1024(blockIdx.x ? b + w * b_pitch : a + w * a_pitch, blockIdx.x ? nb : na, part);
   if (threadIdx.x == 0) rows[w].norms[blockIdx.x] = t;
 }
+// z = a/|a| + i b/|b|, zero-padded to N, row by row (the sectioned form packs na, nb samples of a section pair and divides
+// by the norms of the whole signals)
 __global__ __launch_bounds__(256) void k_xcb_pack(const double* __restrict__ a, int64_t a_pitch, int64_t na,
                                                   const double* __restrict__ b, int64_t b_pitch, int64_t nb,
                                                   const XcbRow* __restrict__ rows, float2* __restrict__ Z, int64_t N) {
@@ -1455,36 +1370,59 @@ __global__ __launch_bounds__(256) void k_xcb_pack(const double* __restrict__ a, 
   const double* br = b + w * b_pitch;
   Z[w * N + i] = make_float2(i < na ? (float)(ar[i] / rows[w].norms[0]) : 0.0f, i < nb ? (float)(br[i] / rows[w].norms[1]) : 0.0f);
 }
+// conj(A_k conj(B_k)) for the second (forward) transform
 __global__ __launch_bounds__(256) void k_xcb_cross(const float2* __restrict__ Z, float2* __restrict__ C, int64_t N) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x, w = blockIdx.y;
   if (k >= N) return;
   const float2 zk = Z[w * N + k], zc = cconj(Z[w * N + ((N - k) & (N - 1))]);
   const float2 A = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
-  const float2 d = csub(zk, zc);
+  const float2 d = csub(zk, zc);                            // 2i B_k  ->  B_k = (d.y, -d.x)/2
   const float2 B = make_float2(0.5f * d.y, -0.5f * d.x);
   const float2 c = cmul(A, cconj(B));
   C[w * N + k] = cconj(c);
 }
-// One workgroup per window: the 'same' span is read straight out of the second transform's output -- the float64 'full'
-// array of the single call, full[j] = (double)Y[(j - (nb-1)) mod N].x / N, is formed value by value and never stored --
-// first argmax (k_xc_argmax's order), then the rival list (k_xc_candidates' rule) in LDS.
-__global__ __launch_bounds__(256) void k_xcb_peak(const float2* __restrict__ Y, int64_t N, int64_t na, int64_t nb, int use_abs,
-                                                  double tol, XcbRow* __restrict__ rows) {
-  __shared__ double bv[256];
-  __shared__ long long bi[256];
+// Where the peak stage reads lag j of row w's 'same' span.  XcLagsOfY: straight out of the second transform's output --
+// full[j] = (double)Y[(j - (nb-1)) mod N].x / N is formed value by value and never stored (the rows of a batch).
+// XcLagsOfFull: the float64 'full' array of ONE row, the same doubles stored (the single pair).
+struct XcLagsOfY {
+  const float2* __restrict__ Y;
+  int64_t N;
+  __device__ auto row(int64_t w, int64_t nb) const {
+    const float2* Yw = Y + w * N;
+    const int64_t n = N, off = (nb - 1) / 2 - (nb - 1);
+    const double dN = (double)N;
+    return [=](int64_t j) { return (double)Yw[(j + off) & (n - 1)].x / dN; };
+  }
+};
+struct XcLagsOfFull {
+  const double* __restrict__ full;
+  __device__ auto row(int64_t, int64_t nb) const {
+    const double* same_span = full + (nb - 1) / 2;
+    return [=](int64_t j) { return same_span[j]; };
+  }
+};
+// One workgroup of T threads per row: the first index of the maximum of the 'same' span (of its magnitude under use_abs),
+// then the rival list in LDS.  Rival peaks: the float32 transform finds the peak to ~1e-6 of its height; a
+// periodic tone, or the +/- lobes under ignore_phase, can put another local maximum within that distance of the top more
+// than two lags away, and the reference's float64 argmax may pick that one.  Every local maximum within `tol` of the
+// transform's top, more than two lags from it, is listed (up to kXcCand of them) for exact re-evaluation.  Nothing here
+// depends on T: the reduction keeps the lowest index of the maximum, and the list is a set that k_xcb_decide orders by
+// (value, lag).  T is 256 beside the other rows of a batch, 1024 where one workgroup scans up to 2^26 lags.
+template <class Lags, int T>
+__global__ __launch_bounds__(T) void k_xcb_peak(Lags src, int64_t na, int64_t nb, int use_abs, double tol, XcbRow* __restrict__ rows) {
+  __shared__ double bv[T];
+  __shared__ long long bi[T];
   __shared__ long long lcand[kXcCand];
   __shared__ int lcount;
   const int64_t w = blockIdx.x;
-  const float2* Yw = Y + w * N;
-  const int64_t off = (nb - 1) / 2 - (nb - 1);
-  const double dN = (double)N;
+  const auto lag = src.row(w, nb);
   auto same = [&](int64_t j) {
-    const double x = (double)Yw[(j + off) & (N - 1)].x / dN;
+    const double x = lag(j);
     return use_abs ? fabs(x) : x;
   };
   double best = -INFINITY;
   long long at = 0;
-  for (int64_t i = threadIdx.x; i < na; i += 256) {
+  for (int64_t i = threadIdx.x; i < na; i += T) {
     const double x = same(i);
     if (x > best) {
       best = x;
@@ -1495,7 +1433,7 @@ __global__ __launch_bounds__(256) void k_xcb_peak(const float2* __restrict__ Y, 
   bi[threadIdx.x] = at;
   if (threadIdx.x == 0) lcount = 0;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
+  for (int o = T / 2; o > 0; o >>= 1) {
     if (threadIdx.x < o) {
       const double x = bv[threadIdx.x + o];
       const long long j = bi[threadIdx.x + o];
@@ -1508,7 +1446,7 @@ __global__ __launch_bounds__(256) void k_xcb_peak(const float2* __restrict__ Y, 
   }
   const long long top = bi[0];
   const double m = same(top);
-  for (int64_t i = threadIdx.x; i < na; i += 256) {
+  for (int64_t i = threadIdx.x; i < na; i += T) {
     if (i >= top - 2 && i <= top + 2) continue;
     const double x = same(i);
     if (!(x >= m - tol)) continue;
@@ -1570,8 +1508,8 @@ __global__ __launch_bounds__(256) void k_xcb_exact7(const double* __restrict__ a
   const double v = xc_exact_256(a + w * a_pitch, na, b + w * b_pitch, nb, r.norms, j, part);
   if (threadIdx.x == 0) r.vals[blockIdx.x] = v;
 }
-// best of arg-2 .. arg+2, the status and parabolic() (util/correlation.py:42-46), one thread per window.  The arithmetic is
-// par_find_delay_f64's host arithmetic, rounding by rounding: no contraction into FMAs here.
+// best of arg-2 .. arg+2, the status and parabolic() (util/correlation.py:42-46), one thread per row.  The arithmetic is
+// numpy's float64, rounding by rounding (f[-1] wraps to the last lag at peak 0): no contraction into FMAs here.
 __global__ __launch_bounds__(64) void k_xcb_final(const XcbRow* __restrict__ rows, int64_t count, int64_t na, int use_abs,
                                                   double* __restrict__ delay, double* __restrict__ corr, int32_t* __restrict__ status) {
 #pragma clang fp contract(off)
@@ -1599,6 +1537,19 @@ __global__ __launch_bounds__(64) void k_xcb_final(const XcbRow* __restrict__ row
   corr[w] = f0 - 0.25 * (fm - fp) * (xv - (double)peak);
   delay[w] = xv - (double)(na / 2);
   status[w] = 0;
+}
+// The delay search of c rows from their lags on (`lags`: the transforms' output, or the one row's 'full' array): peak and
+// rival list -> exact values of the listed lags -> the decision -> seven exact values and the wrap -> delay, corr and
+// status per row.  Everything is decided on the device; nothing here waits for it.
+template <class Lags, int T>
+static void xc_search(Lags lags, const double* a, int64_t a_pitch, int64_t na, const double* b, int64_t b_pitch, int64_t nb,
+                      int64_t c, int ignore_phase, XcbRow* rows, double* delay, double* corr, int32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL((k_xcb_peak<Lags, T>), dim3((unsigned)c), dim3(T), 0, s, lags, na, nb, ignore_phase, kXcRivalTol, rows);
+  hipLaunchKernelGGL(k_xcb_exact_list, dim3(kXcCand, (unsigned)c), dim3(256), 0, s, a, a_pitch, na, b, b_pitch, nb, rows);
+  hipLaunchKernelGGL(k_xcb_decide, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, s, rows, c, ignore_phase);
+  hipLaunchKernelGGL(k_xcb_exact7, dim3(8, (unsigned)c), dim3(256), 0, s, a, a_pitch, na, b, b_pitch, nb, rows);
+  hipLaunchKernelGGL(k_xcb_final, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, s, (const XcbRow*)rows, c, na, ignore_phase, delay, corr,
+                     status);
 }
 
 // out[w][i] = (double)sig[(starts[w] + i - pad_l[w]) * stride] inside the window's samples, 0.0 in its padding
@@ -2504,21 +2455,47 @@ static int64_t xc_fft_len(int64_t na, int64_t nb) {
   while (N < na + nb - 1 && N < kXcMaxFft) N <<= 1;
   return N;
 }
+// The single pair's scratch: Z[N] | Y[N] | 64 bytes | full[na + nb - 1] | the row record | the search's results | spare.
+// The sizes are the ABI's (callers allocate by par_xcorr_scratch_bytes): the row and the results live in the kXcSpare
+// doubles that have always followed the lags.
+constexpr int64_t kXcSpare = 16 + 2 * par::kXcCand + 8;
+struct XcResult {                                // what par_find_delay_f64 copies to the host, once
+  double delay, corr;
+  int32_t status, pad;
+};
+static_assert(sizeof(par::XcbRow) + sizeof(XcResult) <= (size_t)kXcSpare * sizeof(double) && alignof(par::XcbRow) <= sizeof(double),
+              "the single call's row record and results must fit the spare doubles of par_xcorr_scratch_bytes");
 size_t par_xcorr_scratch_bytes(int64_t na, int64_t nb) {
   if (na < 1 || nb < 1) return 0;
-  return (size_t)(2 * xc_fft_len(na, nb) * sizeof(float2) + 64 + (size_t)(na + nb + 16 + 2 * par::kXcCand + 8) * sizeof(double));
+  return (size_t)(2 * xc_fft_len(na, nb) * sizeof(float2) + 64 + (size_t)(na + nb + kXcSpare) * sizeof(double));
+}
+struct XcScratch {
+  float2 *Z, *Y;
+  double* full;
+  par::XcbRow* row;
+  XcResult* res;
+};
+static XcScratch xc_scratch(void* scratch, int64_t N, int64_t na, int64_t nb) {
+  XcScratch sc;
+  sc.Z = static_cast<float2*>(scratch);
+  sc.Y = sc.Z + N;
+  sc.full = reinterpret_cast<double*>(reinterpret_cast<char*>(sc.Y + N) + 64);
+  sc.row = reinterpret_cast<par::XcbRow*>(sc.full + (na + nb - 1));
+  sc.res = reinterpret_cast<XcResult*>(sc.row + 1);
+  return sc;
 }
 
-static int xcorr_full(int device, const double* a, int64_t na, const double* b, int64_t nb, void* scratch, double* full,
-                      double** norms_out, hipStream_t s) {
+// The correlation of one pair as a batch of one row: norms into the row record, then pack -> transform -> cross spectrum
+// -> transform -> `full`, section pair by section pair where one transform does not hold the lags.
+static int xcorr_full(int device, const double* a, int64_t na, const double* b, int64_t nb, const XcScratch& sc, double* full,
+                      hipStream_t s) {
   using namespace par;
   const int64_t N = xc_fft_len(na, nb);
   PAR_REQUIRE(na <= kXcMaxLen && nb <= kXcMaxLen, PAR_ERR_UNSUPPORTED, "xcorr: %lld / %lld samples (limit 2^25 per signal)",
               (long long)na, (long long)nb);
-  float2* Z = static_cast<float2*>(scratch);
-  float2* Y = Z + N;
-  double* norms = reinterpret_cast<double*>(Y + N);
-  hipLaunchKernelGGL(k_xc_norms, dim3(2), dim3(1024), 0, s, a, na, b, nb, norms);
+  float2 *Z = sc.Z, *Y = sc.Y;
+  const dim3 gN((unsigned)ceil_div(N, 256));
+  hipLaunchKernelGGL(k_xcb_norms, dim3(2), dim3(1024), 0, s, a, na, na, b, nb, nb, sc.row);
   if (na + nb - 1 > N) {
     // Windows of more than ~2.7 s at 192 kHz: correlation is bilinear, so the signals are cut into sections of 2^19
     // samples and every pair (p, q) adds its 2^20-point correlation into full at the lag offset p - q sections.  The
@@ -2528,11 +2505,10 @@ static int xcorr_full(int device, const double* a, int64_t na, const double* b, 
       const int64_t la = na - pa < kXcSection ? na - pa : kXcSection;
       for (int64_t qb = 0; qb < nb; qb += kXcSection) {
         const int64_t lb = nb - qb < kXcSection ? nb - qb : kXcSection;
-        hipLaunchKernelGGL(k_xc_pack, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, a + pa, la, b + qb, lb,
-                           (const double*)norms, Z, N);
+        hipLaunchKernelGGL(k_xcb_pack, gN, dim3(256), 0, s, a + pa, la, la, b + qb, lb, lb, (const XcbRow*)sc.row, Z, N);
         int rc = big_fft_c2c(device, Z, Y, N, 1, s);
         if (rc != PAR_OK) return rc;
-        hipLaunchKernelGGL(k_xc_cross, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, (const float2*)Y, Z, N);
+        hipLaunchKernelGGL(k_xcb_cross, gN, dim3(256), 0, s, (const float2*)Y, Z, N);
         rc = big_fft_c2c(device, Z, Y, N, 1, s);
         if (rc != PAR_OK) return rc;
         // local index jl = lag + lb - 1; global index = lag + (pa - qb) + nb - 1
@@ -2542,19 +2518,17 @@ static int xcorr_full(int device, const double* a, int64_t na, const double* b, 
       }
     }
     PAR_HIP_CHECK(hipGetLastError());
-    *norms_out = norms;
     return PAR_OK;
   }
-  hipLaunchKernelGGL(k_xc_pack, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, a, na, b, nb, (const double*)norms, Z, N);
+  hipLaunchKernelGGL(k_xcb_pack, gN, dim3(256), 0, s, a, na, na, b, nb, nb, (const XcbRow*)sc.row, Z, N);
   int rc = big_fft_c2c(device, Z, Y, N, 1, s);                       // Y = FFT(a + i b)
   if (rc != PAR_OK) return rc;
-  hipLaunchKernelGGL(k_xc_cross, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, (const float2*)Y, Z, N);
+  hipLaunchKernelGGL(k_xcb_cross, gN, dim3(256), 0, s, (const float2*)Y, Z, N);
   rc = big_fft_c2c(device, Z, Y, N, 1, s);                           // Y = conj(N * circular correlation)
   if (rc != PAR_OK) return rc;
   hipLaunchKernelGGL(k_xc_unpack, dim3((unsigned)ceil_div(na + nb - 1, 256)), dim3(256), 0, s, (const float2*)Y, N, nb,
                      na + nb - 1, full);
   PAR_HIP_CHECK(hipGetLastError());
-  *norms_out = norms;
   return PAR_OK;
 }
 
@@ -2564,14 +2538,17 @@ int par_xcorr_f64(int device, const double* a, int64_t na, const double* b, int6
   PAR_REQUIRE(a && b && scratch && full && na >= 1 && nb >= 1, PAR_ERR_ARG, "par_xcorr_f64: bad args");
   PAR_REQUIRE(scratch_bytes >= par_xcorr_scratch_bytes(na, nb), PAR_ERR_WORKSPACE, "par_xcorr_f64: scratch too small");
   PAR_HIP_CHECK(hipSetDevice(device));
-  double* norms;
-  return xcorr_full(device, a, na, b, nb, scratch, full, &norms, as_stream(stream));
+  return xcorr_full(device, a, na, b, nb, xc_scratch(scratch, xc_fft_len(na, nb), na, nb), full, as_stream(stream));
 }
 
 // find_delay(a, b, ignore_phase) of util/correlation.py:16-39 (windows are applied by the caller, in place, like the
 // reference): *delay = parabola-refined peak of the 'same' correlation minus len//2, *corr = its height.  The peak is
 // located by the float32 transform and the lags around it are re-evaluated as float64 dot products.  A peak on the last
-// lag is the reference's IndexError (PAR_ERR_INDEX).  Synchronises.
+// lag is the reference's IndexError (PAR_ERR_INDEX).  The batch of one row, with one difference in where the peak stage
+// reads: a batch row's lags come straight out of its transform (at most 2^20 of them, one 256-thread workgroup per row);
+// here ONE workgroup has up to 2^26 lags to scan, so the lags are first formed as the float64 'full' array by a full grid
+// (sums over section pairs in the sectioned form) and scanned by 1024 threads.  The doubles compared are the same.
+// Synchronises once, for the copy of delay, corr and status to the host.
 int par_find_delay_f64(int device, const double* a, int64_t na, const double* b, int64_t nb, int ignore_phase, void* scratch,
                        size_t scratch_bytes, double* delay, double* corr, void* stream) {
   using namespace par;
@@ -2579,78 +2556,19 @@ int par_find_delay_f64(int device, const double* a, int64_t na, const double* b,
   PAR_REQUIRE(scratch_bytes >= par_xcorr_scratch_bytes(na, nb), PAR_ERR_WORKSPACE, "par_find_delay_f64: scratch too small");
   PAR_HIP_CHECK(hipSetDevice(device));
   hipStream_t s = as_stream(stream);
-  const int64_t N = xc_fft_len(na, nb);
-  double* full = reinterpret_cast<double*>(static_cast<char*>(scratch) + 2 * N * sizeof(float2) + 64);
-  double* norms;
-  int rc = xcorr_full(device, a, na, b, nb, scratch, full, &norms, s);
+  const XcScratch sc = xc_scratch(scratch, xc_fft_len(na, nb), na, nb);
+  const int rc = xcorr_full(device, a, na, b, nb, sc, sc.full, s);
   if (rc != PAR_OK) return rc;
-  long long* arg = reinterpret_cast<long long*>(norms + 2);
-  double* vals = full + (na + nb - 1);                                 // 7 values behind the correlation (scratch holds 16 spare)
-  const double* same = full + (nb - 1) / 2;                            // 'same': na values centred on the full output
-  hipLaunchKernelGGL(k_xc_argmax, dim3(1), dim3(1024), 0, s, same, na, ignore_phase, arg);
-  {
-    // rival peaks within the float32 transform's error of the top: exact values decide, the lowest lag wins a tie
-    // (np.argmax returns the first maximum)
-    long long* cand = reinterpret_cast<long long*>(vals + 8);
-    double* cvals = vals + 8 + kXcCand;
-    int* n_cand = reinterpret_cast<int*>(cvals + kXcCand);
-    PAR_HIP_CHECK(hipMemsetAsync(n_cand, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_xc_candidates, dim3(1), dim3(1024), 0, s, same, na, ignore_phase, (const long long*)arg, kXcRivalTol, cand,
-                       n_cand);
-    int nc = 0;
-    long long top = 0;
-    PAR_HIP_CHECK(hipMemcpyAsync(&nc, n_cand, sizeof(int), hipMemcpyDeviceToHost, s));
-    PAR_HIP_CHECK(hipMemcpyAsync(&top, arg, sizeof(top), hipMemcpyDeviceToHost, s));
-    PAR_HIP_CHECK(hipStreamSynchronize(s));
-    if (nc > 0 && nc < kXcCand) {                        // the top goes into slot nc: nc + 1 entries must fit the kXcCand slots;
-                                                         // as many rivals as slots or more: a plateau, the transform's top stands
-      long long lags[kXcCand + 1];
-      double ex[kXcCand + 1];
-      PAR_HIP_CHECK(hipMemcpyAsync(lags, cand, nc * sizeof(long long), hipMemcpyDeviceToHost, s));
-      PAR_HIP_CHECK(hipStreamSynchronize(s));
-      lags[nc] = top;
-      PAR_HIP_CHECK(hipMemcpyAsync(cand, lags, (nc + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_xc_exact_list, dim3((unsigned)(nc + 1)), dim3(256), 0, s, a, na, b, nb, (const double*)norms,
-                         (const long long*)cand, cvals);
-      PAR_HIP_CHECK(hipMemcpyAsync(ex, cvals, (nc + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
-      PAR_HIP_CHECK(hipStreamSynchronize(s));
-      int best = nc;
-      for (int c = 0; c < nc; ++c) {
-        const double x = ignore_phase ? fabs(ex[c]) : ex[c], y = ignore_phase ? fabs(ex[best]) : ex[best];
-        if (x > y || (x == y && lags[c] < lags[best])) best = c;
-      }
-      if (lags[best] != top) PAR_HIP_CHECK(hipMemcpyAsync(arg, &lags[best], sizeof(long long), hipMemcpyHostToDevice, s));
-    }
-  }
-  // exact values at arg-3 .. arg+3; the final peak is the best of arg-2 .. arg+2
-  hipLaunchKernelGGL(k_xc_exact, dim3(7), dim3(256), 0, s, a, na, b, nb, (const double*)norms, (const long long*)arg, (int64_t)-3,
-                     vals);
+  xc_search<XcLagsOfFull, 1024>(XcLagsOfFull{sc.full}, a, na, na, b, nb, nb, 1, ignore_phase, sc.row, &sc.res->delay, &sc.res->corr,
+                                &sc.res->status, s);
   PAR_HIP_CHECK(hipGetLastError());
-  long long p0 = 0;
-  double v[7];
-  PAR_HIP_CHECK(hipMemcpyAsync(&p0, arg, sizeof(p0), hipMemcpyDeviceToHost, s));
-  PAR_HIP_CHECK(hipMemcpyAsync(v, vals, sizeof(v), hipMemcpyDeviceToHost, s));
+  XcResult r;
+  PAR_HIP_CHECK(hipMemcpyAsync(&r, sc.res, sizeof(r), hipMemcpyDeviceToHost, s));
   PAR_HIP_CHECK(hipStreamSynchronize(s));
-  int best = 3;
-  for (int c = 1; c <= 5; ++c) {
-    const long long j = p0 - 3 + c;
-    if (j < 0 || j >= na) continue;
-    const double x = ignore_phase ? fabs(v[c]) : v[c], y = ignore_phase ? fabs(v[best]) : v[best];
-    if (x > y || (x == y && c < best)) best = c;
-  }
-  const long long peak = p0 - 3 + best;
-  PAR_REQUIRE(peak != na - 1, PAR_ERR_INDEX, "par_find_delay_f64: correlation peak on the last lag (index %lld is out of bounds "
+  PAR_REQUIRE(r.status != 1, PAR_ERR_INDEX, "par_find_delay_f64: correlation peak on the last lag (index %lld is out of bounds "
               "for axis 0 with size %lld in the reference's parabolic())", (long long)na, (long long)na);
-  double fm = v[best - 1], f0 = v[best], fp = v[best + 1];
-  if (peak == 0) {                                                     // f[-1]: numpy wraps to the last element
-    hipLaunchKernelGGL(k_xc_exact, dim3(1), dim3(256), 0, s, a, na, b, nb, (const double*)norms, (const long long*)arg,
-                       (int64_t)(na - 1 - p0), vals);
-    PAR_HIP_CHECK(hipMemcpyAsync(&fm, vals, sizeof(double), hipMemcpyDeviceToHost, s));
-    PAR_HIP_CHECK(hipStreamSynchronize(s));
-  }
-  const double xv = 0.5 * (fm - fp) / (fm - 2.0 * f0 + fp) + (double)peak;
-  *corr = f0 - 0.25 * (fm - fp) * (xv - (double)peak);
-  *delay = xv - (double)(na / 2);
+  *delay = r.delay;
+  *corr = r.corr;
   return PAR_OK;
 }
 
@@ -2711,14 +2629,8 @@ int par_find_delay_batch_f64(int device, double* a, int64_t a_pitch, int64_t na,
     hipLaunchKernelGGL(k_xcb_cross, gN, dim3(256), 0, s, (const float2*)Y, Z, N);
     rc = big_fft_c2c(device, Z, Y, N, c, s);                            // Y = conj(N * circular correlation)
     if (rc != PAR_OK) return rc;
-    hipLaunchKernelGGL(k_xcb_peak, dim3((unsigned)c), dim3(256), 0, s, (const float2*)Y, N, na, nb, ignore_phase, kXcRivalTol, rows);
-    hipLaunchKernelGGL(k_xcb_exact_list, dim3(kXcCand, (unsigned)c), dim3(256), 0, s, (const double*)ac, a_pitch, na, (const double*)bc,
-                       b_pitch, nb, rows);
-    hipLaunchKernelGGL(k_xcb_decide, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, s, rows, c, ignore_phase);
-    hipLaunchKernelGGL(k_xcb_exact7, dim3(8, (unsigned)c), dim3(256), 0, s, (const double*)ac, a_pitch, na, (const double*)bc, b_pitch,
-                       nb, rows);
-    hipLaunchKernelGGL(k_xcb_final, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, s, (const XcbRow*)rows, c, na, ignore_phase,
-                       delay + w0, corr + w0, status + w0);
+    xc_search<XcLagsOfY, 256>(XcLagsOfY{Y, N}, ac, a_pitch, na, bc, b_pitch, nb, c, ignore_phase, rows, delay + w0, corr + w0, status + w0,
+                              s);
     PAR_HIP_CHECK(hipGetLastError());
   }
   return PAR_OK;

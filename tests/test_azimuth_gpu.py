@@ -85,8 +85,10 @@ def single(C, a, b, ign, window_name):
 @pytest.mark.parametrize("ign", [False, True])
 @pytest.mark.parametrize("na,nb", A.BATCH_SHAPES)
 def test_batch_equals_single_call(C, na, nb, ign, window_name):
-    """W = 1, 2, 37 rows of white, narrow-band and tone takes: find_delay_batch equals find_delay row by row, bit for bit, both lie
-    within 4 x delay_bounds of the fsum oracle; pitched rows, sentinels around the outputs, a second run identical"""
+    """W = 1, 2, 37 rows of white, narrow-band and tone takes: find_delay_batch equals find_delay row by row, bit for bit.  The single
+    call is the batch of one row through the same kernels, so the equality says that a row's result does not depend on its
+    neighbours, its pitch, W or the entry point; the accuracy statement is the pin of every row to the fsum oracle within
+    4 x delay_bounds.  Pitched rows, sentinels around the outputs, a second run identical"""
     a, b = A.batch_rows(na, nb, max(A.BATCH_WS))
     want_d, want_c = single(C, a, b, ign, window_name)
     wa = scipy.signal.get_window(window_name, na) if window_name else 1.0

@@ -146,6 +146,57 @@ def test_find_delay_edge_lags(C, na, nb):
         C.find_delay(a.copy(), b.copy())
 
 
+def test_find_delay_edge_lags_sectioned(C):
+    """the same where the peak stage scans the float64 'full' array of 2 x 2 section pairs with 1024 threads, which no batch reaches:
+    peaks on lag 0 (f[-1], the eighth exact value) and na-2 under both ignore_phase settings, within 4 x delay_bounds of the fsum
+    oracle (about 1.07e-9 samples and 5.8e-10 corr: tests/test_xcorr_inputs_cpu.py); a peak on na-1 is the reference's IndexError"""
+    na, nb = X.SECTIONED_SHAPES[0]
+    for want in X.sectioned_edge_peaks():
+        a, b = X.edge_case(na, nb, want)
+        for ign in (False, True):
+            o = X.oracle_delay(a, b, ign)
+            got = C.find_delay(a.copy(), b.copy(), ignore_phase=ign)
+            r = _held(got, o, nb)
+            print(f"\nsectioned edge lag {want} ign {ign}: delay error {r[0]:.2e}, corr error {r[1]:.2e} of the derived bounds", end="")
+            assert o.peak == want and round(got[0] + na // 2) == want, (want, ign, got)
+            assert max(r) <= SAFETY, (want, ign, got, o, r)
+    a, b = X.edge_case(na, nb, na - 1)
+    with pytest.raises(IndexError):
+        C.find_delay(a.copy(), b.copy())
+
+
+@pytest.mark.parametrize("na,nb", X.SCRATCH_SHAPES)
+def test_single_calls_stay_inside_their_scratch(C, na, nb):
+    """par_find_delay_f64 and par_xcorr_f64 at the ABI, on a scratch of exactly par_xcorr_scratch_bytes(na, nb) bytes followed by 256
+    sentinel bytes: the row record and the results of the delay search live in the spare room behind
+    the lags, and must not leave it.  The sentinels (behind `full` too) keep their bits, and a second call on the used scratch gives
+    the same bits."""
+    import ctypes
+    import torch
+    from pyaudiorestoration_amd import _dev, _lib
+    L = _lib.lib()
+    a, b = X.signal_pair("white", na, nb)
+    a_t, b_t = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    nbytes, guard, n_full = int(L.par_xcorr_scratch_bytes(na, nb)), 256, na + nb - 1
+    scratch = torch.full((nbytes + guard,), 0xA5, dtype=torch.uint8, device="cuda")
+    full = torch.full((n_full + 32,), -7.25e11, dtype=torch.float64, device="cuda")
+    runs = []
+    for _ in range(2):
+        delay, corr = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        for ign in (0, 1):
+            _lib.check(L.par_find_delay_f64(0, _dev.ptr(a_t), na, _dev.ptr(b_t), nb, ign, _dev.ptr(scratch), nbytes, ctypes.byref(delay),
+                                            ctypes.byref(corr), _dev.stream_ptr(0)))
+        _lib.check(L.par_xcorr_f64(0, _dev.ptr(a_t), na, _dev.ptr(b_t), nb, _dev.ptr(scratch), nbytes, _dev.ptr(full), _dev.stream_ptr(0)))
+        torch.cuda.synchronize()
+        f = full.cpu().numpy()
+        assert np.all(scratch[nbytes:].cpu().numpy() == 0xA5) and np.all(f[n_full:] == -7.25e11)
+        assert np.isfinite(delay.value) and np.isfinite(corr.value) and np.all(np.isfinite(f[:n_full]))
+        runs.append((bits(np.array([delay.value, corr.value])), bits(f)))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
+    o = X.oracle_delay(a, b, True)                                                   # the last call ignored the phase
+    assert max(_held((delay.value, corr.value), o, nb)) <= SAFETY, (delay.value, corr.value, o)
+
+
 def test_correlate_sources_device_tensors_of_unequal_length(C):
     """pytapesynch_gui.py:108-133 hands find_delay whatever get_signal_around returned: under match_speed the source window is
     t_width / speed long and resampled, so len(src) != len(ref) is ACCEPTED there, never checked -- and so it is here.  Device

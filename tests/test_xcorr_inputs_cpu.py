@@ -49,6 +49,35 @@ def test_edge_lag_builders_peak_where_they_say(na, nb):
             assert abs(o.fm - same[want - 1]) <= X.delta_f(nb)            # want == 0: same[-1], the wrapped read
 
 
+def test_sectioned_edge_lag_builders_peak_where_they_say():
+    """the same in the sectioned regime (2 x 2 section pairs, the float64 'full' array under the peak stage): lag 0 and lag na-2 under
+    both ignore_phase settings, no rival, and the 4 x bounds the GPU test holds; a peak on na-1 is the IndexError"""
+    na, nb = X.SECTIONED_SHAPES[0]
+    assert X.section_counts(na, nb) == (2, 2) and X.sectioned_edge_peaks() == (0, na - 2)
+    for want in X.sectioned_edge_peaks():
+        a, b = X.edge_case(na, nb, want)
+        same = X.same_fft(a, b)
+        for ign, v in ((False, same), (True, np.abs(same))):
+            top, rivals = X.rivals_of(v)
+            assert top == want and len(rivals) == 0
+            o = X.oracle_delay(a, b, ign)
+            bd, bc = X.delay_bounds(o.fm, o.f0, o.fp, nb)
+            print(f"\nsectioned edge lag {want} ign {ign}: 4 x bounds {4 * bd:.3e} samples, {4 * bc:.3e} corr", end="")
+            assert o.peak == want and 4 * bd < 2e-9 and 4 * bc < 1e-9
+    a, b = X.edge_case(na, nb, na - 1)
+    assert int(np.argmax(X.same_fft(a, b))) == na - 1
+    with pytest.raises(IndexError):
+        X.oracle_delay(a, b)
+
+
+def test_scratch_shapes_cover_the_layouts():
+    """the smallest transform, the smallest member of the next size (the most spare room in the transform arrays), the sectioned form"""
+    assert [X.xc_fft_len(na, nb) for na, nb in X.SCRATCH_SHAPES] == [1 << 13, 1 << 14, 1 << 20]
+    assert [X.section_counts(na, nb) for na, nb in X.SCRATCH_SHAPES] == [(1, 1), (1, 1), (2, 2)]
+    na, nb = X.SCRATCH_SHAPES[1]
+    assert na + nb - 1 == (1 << 13) + 1
+
+
 def _rival_checks(a, b, lags, loud, K, ignore_phase=False):
     same = X.same_fft(a, b)
     v = np.abs(same) if ignore_phase else same

@@ -90,8 +90,8 @@ def oracle_delay(a, b, ignore_phase=False, near=1e-12):
 
 
 def rivals_of(v, tol=RIVAL_TOL):
-    """the listing rule of k_xc_candidates applied to v (|same| under ignore_phase): local maxima within tol of the top,
-    more than two lags from it -> (top, rival lags)"""
+    """the listing rule of the peak stage (k_xcb_peak, the one the single and the batched search share) applied to v
+    (|same| under ignore_phase): local maxima within tol of the top, more than two lags from it -> (top, rival lags)"""
     v = np.asarray(v)
     top = int(np.argmax(v))
     left = np.concatenate(([-np.inf], v[:-1]))
@@ -201,6 +201,13 @@ def size_classes():
 
 SECTIONED_SHAPES = ((524_289, 524_289), (700_001, 524_289))
 KINDS = ("white", "narrow", "tone", "dc")
+# the scratch layout of the single call at the ABI: the smallest transform, the smallest member of the next one, the sectioned form
+SCRATCH_SHAPES = ((1000, 999), (4097, 4097), SECTIONED_SHAPES[0])
+
+
+def sectioned_edge_peaks():
+    """edge_case peaks for SECTIONED_SHAPES[0]: lag 0 (f[-1] wraps to the last lag) and the last lag but one"""
+    return (0, SECTIONED_SHAPES[0][0] - 2)
 
 
 def signal_pair(kind, na, nb, seed=0):
