@@ -366,12 +366,19 @@ int par_track_cog_f64(int device, const float* mag, int64_t n_frames, int bins, 
  *            in the data, the host applies scipy's own construction to the identity)
  *   wind     device f64 [n] = np.hanning(n)
  *   log_span = log2 f[NU-1] - log2 f[NL], log_mean = log2((fL + fU)/2): the reference's final scaling
- *   work     device f64 [par_track_corr_work_len(count, n)];  freqs  device f64 [count] out
- *   status   device int32 scratch.  A peak on the last lag is the reference's IndexError: PAR_ERR_INDEX.  Synchronises. */
+ *   work     device f64 [par_track_corr_work_len(count, n)] = (count + 1) n + count.  On return it holds R[count + 1][n], the
+ *            windowed resampled rows (row `count` = wind: the reference's all-ones frame), then changes[count] = n/2 - refined
+ *            peak lag of rows i, i + 1 (NaN where a row's norm is 0: np.argmax returns the first NaN);  freqs  device f64 [count]
+ *            out = exp2(log_mean + cumsum(changes) / n * log_span)
+ *   status   device int32 scratch.  A peak on the last lag is the reference's IndexError: PAR_ERR_INDEX.  Synchronises.
+ *   mag_pitch in (0, bins): PAR_ERR_ARG, here and in par_piptrack_f32, before any device call. */
 /* PartialsTracker's librosa.piptrack (util/wow_detection.py:361-387; third-party routine, restated from librosa 0.10's
  * published source, parity unpinned): thresholded local maxima of every magnitude column inside [fmin, fmax), refined by
- * a parabola.  mag: device f32 [n_frames][bins] as par_stft_f32 mode 1 writes it; S = (mag - offset) * scale gives the
- * |stft| librosa works on (offset 1e-7, scale sqrt(n_fft)).  pitches / mags: device f32 [n_frames][bins] out. */
+ * a parabola.  mag: device f32 [n_frames][bins] as par_stft_f32 mode 1 writes it; S = |(mag - offset) * scale| gives the
+ * |stft| librosa works on (offset 1e-7, scale sqrt(n_fft)); piptrack takes |S| as librosa does (np.abs(S)), so a cell below
+ * `offset` counts by its size.  bins may be less than fft_size / 2 + 1 (the lowest rows of the spectrum).  pitches / mags: device
+ * f32 [n_frames][bins] out; mags round as numpy's float32 does (S + fl(fl(0.5 avg) shift): two roundings, no fused
+ * multiply-add), and both maps equal the float32 restatement bit for bit.  NaN / inf magnitudes: unspecified. */
 int par_piptrack_f32(int device, const float* mag, int64_t n_frames, int bins, int64_t mag_pitch, float scale, float offset, int fft_size,
                      double sr, double fmin, double fmax, float threshold, float* pitches, float* mags, void* stream);
 int64_t par_track_corr_work_len(int64_t count, int n);

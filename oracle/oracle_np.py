@@ -427,7 +427,7 @@ def piptrack(S, sr, n_fft, fmin=150.0, fmax=4000.0, threshold=0.1):
     S = np.abs(np.asarray(S))
     fmin = np.maximum(fmin, 0)
     fmax = np.minimum(fmax, float(sr) / 2)
-    fft_freqs = np.fft.rfftfreq(n_fft, 1.0 / sr)
+    fft_freqs = np.fft.rfftfreq(n_fft, 1.0 / sr)[:S.shape[-2]]   # S may hold only the lowest rows of the n_fft-point spectrum
     avg = np.gradient(S, axis=-2)
     a = S[2:] + S[:-2] - 2 * S[1:-1]                       # _parabolic_interpolation along the frequency axis
     b = (S[2:] - S[:-2]) / 2

@@ -415,8 +415,9 @@ __global__ __launch_bounds__(256) void k_zc_write(const double* __restrict__ x, 
 // per frame, every local maximum of the thresholded magnitude column inside [fmin, fmax) becomes a pitch
 //   (k + shift) sr / n_fft,  shift = -b/a,  a = S[k+1] + S[k-1] - 2 S[k],  b = (S[k+1] - S[k-1]) / 2   (0 unless |b| < |a|)
 // with magnitude S[k] + b shift / 2; everything else is 0.  Threshold = `threshold` x the column maximum; local maximum:
-// x[k] > x[k-1] and x[k] >= x[k+1] on the edge-padded, thresholded column.  One wave per frame; S = (mag - offset) * scale
-// undoes get_mag's + 1e-7 and 1/sqrt(n_fft) so the magnitudes are librosa's |stft|.
+// x[k] > x[k-1] and x[k] >= x[k+1] on the edge-padded, thresholded column.  One wave per frame; S = |(mag - offset) * scale|
+// undoes get_mag's + 1e-7 and 1/sqrt(n_fft) so the magnitudes are librosa's |stft|.  Every float32 operation is rounded where
+// numpy rounds it: pitches and magnitudes equal numpy's float32 evaluation of the same S bit for bit (tests/test_track_abi_gpu.py).
 __global__ __launch_bounds__(256) void k_piptrack(const float* __restrict__ mag, int bins, int64_t pitch, int64_t n_frames, float scale,
                                                   float offset, int fft_size, double sr, double fmin, double fmax,
                                                   float threshold, float* __restrict__ pitches, float* __restrict__ mags) {
@@ -425,8 +426,9 @@ __global__ __launch_bounds__(256) void k_piptrack(const float* __restrict__ mag,
   if (fr >= n_frames) return;
   const float* row = mag + fr * pitch;
   float m = -INFINITY;
+  const auto S = [&](int k) { return fabsf((row[k] - offset) * scale); };   // librosa starts with np.abs(S)
   for (int k = lane; k < bins; k += kWave) {
-    const float x = (row[k] - offset) * scale;
+    const float x = S(k);
     m = x > m ? x : m;
   }
 #pragma unroll
@@ -436,9 +438,9 @@ __global__ __launch_bounds__(256) void k_piptrack(const float* __restrict__ mag,
   }
   const float ref = threshold * m;
   for (int k = lane; k < bins; k += kWave) {
-    const float x = (row[k] - offset) * scale;
-    const float xm = k > 0 ? (row[k - 1] - offset) * scale : x;
-    const float xp = k + 1 < bins ? (row[k + 1] - offset) * scale : x;
+    const float x = S(k);
+    const float xm = k > 0 ? S(k - 1) : x;
+    const float xp = k + 1 < bins ? S(k + 1) : x;
     const float t = x > ref ? x : 0.0f, tm = xm > ref ? xm : 0.0f, tp = xp > ref ? xp : 0.0f;
     const double f = (double)k * sr / (double)fft_size;
     float pitch = 0.0f, magv = 0.0f;
@@ -450,7 +452,13 @@ __global__ __launch_bounds__(256) void k_piptrack(const float* __restrict__ mag,
         avg = b;
       }
       pitch = (float)(((double)k + (double)shift) * sr / (double)fft_size);
-      magv = x + 0.5f * avg * shift;
+      {
+        // numpy rounds dskew = 0.5 * avg * shift to float32 before S + dskew: two roundings, a contracted v_fma_f32 makes one
+        // (HIP's __fmul_rn / __fadd_rn are plain operators and contract like them; the pragma holds for this block alone)
+#pragma clang fp contract(off)
+        const float dskew = 0.5f * avg * shift;
+        magv = x + dskew;
+      }
     }
     pitches[fr * bins + k] = pitch;
     mags[fr * bins + k] = magv;
@@ -636,6 +644,8 @@ int par_track_corr_f64(int device, const float* mag, int64_t n_frames, int bins,
                        double* freqs, int32_t* status, void* stream) {
   using namespace par;
   PAR_REQUIRE(mag && M && wind && work && freqs && status, PAR_ERR_ARG, "par_track_corr_f64: null pointer");
+  const int64_t pitch = mag_pitch ? mag_pitch : bins;
+  PAR_REQUIRE(pitch >= bins, PAR_ERR_ARG, "par_track_corr_f64: mag_pitch < bins");
   // NU may reach past the last bin: the reference's slices [NL:NU] clip to the spectrum while its grid keeps
   // 4 (NU - NL) points (util/wow_detection.py:404-406), so the band has nb = min(NU, bins) - NL values and M is [n][nb]
   const int nb = (NU < bins ? NU : bins) - NL;
@@ -658,7 +668,7 @@ int par_track_corr_f64(int device, const float* mag, int64_t n_frames, int bins,
       done.insert(device);
     }
   }
-  hipLaunchKernelGGL(k_corr_resample, dim3((unsigned)(count + 1)), dim3(256), band_lds, s, mag, mag_pitch ? mag_pitch : (int64_t)bins, NL, nb,
+  hipLaunchKernelGGL(k_corr_resample, dim3((unsigned)(count + 1)), dim3(256), band_lds, s, mag, pitch, NL, nb,
                      count, M, wind, n, R);
   const size_t ab_lds = 2 * (size_t)n * sizeof(double);
   if (ab_lds <= 131072) {                                  // n <= 8192: both frames in LDS (up to 128 of the CU's 160 KB)
@@ -691,12 +701,13 @@ int par_piptrack_f32(int device, const float* mag, int64_t n_frames, int bins, i
   using namespace par;
   PAR_REQUIRE(mag && pitches && mags, PAR_ERR_ARG, "par_piptrack_f32: null pointer");
   PAR_REQUIRE(n_frames >= 0 && bins >= 2 && fft_size >= 2 && sr > 0, PAR_ERR_ARG, "par_piptrack_f32: bad sizes");
+  const int64_t pitch = mag_pitch ? mag_pitch : bins;
+  PAR_REQUIRE(pitch >= bins, PAR_ERR_ARG, "par_piptrack_f32: mag_pitch < bins");
   if (n_frames == 0) return PAR_OK;
   PAR_HIP_CHECK(hipSetDevice(device));
   fmin = fmin > 0.0 ? fmin : 0.0;
   fmax = fmax < sr / 2 ? fmax : sr / 2;
-  hipLaunchKernelGGL(k_piptrack, dim3((unsigned)ceil_div(n_frames, 4)), dim3(256), 0, as_stream(stream), mag, bins,
-                     mag_pitch ? mag_pitch : (int64_t)bins, n_frames, scale,
+  hipLaunchKernelGGL(k_piptrack, dim3((unsigned)ceil_div(n_frames, 4)), dim3(256), 0, as_stream(stream), mag, bins, pitch, n_frames, scale,
                      offset, fft_size, sr, fmin, fmax, threshold, pitches, mags);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
