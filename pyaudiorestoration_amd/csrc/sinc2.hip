@@ -1237,14 +1237,15 @@ static int64_t stream_wave_slots(int device) {
 }
 
 // the launch's arguments and its grid for one file
-static int64_t make_stream_args(int device, int64_t len_out, const float* sig, int64_t len_in, float* out, const FusedArgs& fa,
-                                const float4* tab, const TapModes& tmd, int64_t pick_out_stride, S2Args& a) {
+static int64_t make_stream_args(int device, const SincFile& f, const float4* tab, const TapModes& tmd, int64_t pick_out_stride, S2Args& a) {
   const int64_t slots = stream_wave_slots(device);
+  const int64_t len_out = f.len_out;
+  const FusedArgs& fa = f.fa;
   a.out_stride = pick_out_stride;
   a.len_out = len_out;
-  a.sig = sig;
-  a.len_in = len_in;
-  a.out = out;
+  a.sig = f.sig;
+  a.len_in = f.len_in;
+  a.out = f.out;
   a.hdr = fa.hdr;
   a.rec = fa.rec;
   a.rec2 = fa.rec2;
@@ -1282,42 +1283,48 @@ static int64_t make_stream_args(int device, int64_t len_out, const float* sig, i
   return a.n_big + ceil_div(a.n_full - a.n_big * a.tiles, (int64_t)a.tiles_tail) + a.n_edge;
 }
 
-int launch_sinc_stream(int device, int64_t len_out, const float* sig, int64_t len_in, float* out, const FusedArgs& fa,
-                       const float4* tab, const TapModes& tmd, hipStream_t s, int nch, int64_t pick_out_stride) {
+int launch_sinc_stream(int device, SincRoute route, const SincFile& f, int64_t pick_out_stride, const float4* tab, const TapModes& tmd,
+                       hipStream_t s) {
   S2Args a;
-  const int64_t grid = make_stream_args(device, len_out, sig, len_in, out, fa, tab, tmd, pick_out_stride, a);
-  if (grid > 0 && nch == 2 && pick_out_stride > 0) {
-    hipLaunchKernelGGL((k_sinc_pipe<2, 3>), dim3((unsigned)grid), dim3(kWave), 0, s, a);
-  } else if (grid > 0 && nch == 2) {
-    hipLaunchKernelGGL((k_sinc_pipe<2, 0>), dim3((unsigned)grid), dim3(kWave), 0, s, a);
-  } else if (grid > 0) {
-    // mono: the streams with an fc < 1 tile (two waves per SIMD: all 25 constant fragments) and the end tiles, then the fc = 1
-    // streams (three per SIMD), over the same grid -- a wave of the other kind leaves behind its tile headers
-    hipLaunchKernelGGL((k_sinc_pipe<1, 2>), dim3((unsigned)grid), dim3(kWave), 0, s, a);
-    hipLaunchKernelGGL((k_sinc_pipe<1, 1>), dim3((unsigned)grid), dim3(kWave), 0, s, a);
+  const int64_t grid = make_stream_args(device, f, tab, tmd, route == SincRoute::StreamPick ? pick_out_stride : 0, a);
+  const dim3 g((unsigned)grid), b(kWave);
+  if (route == SincRoute::Block) return PAR_ERR_ARG;
+  if (grid > 0) {
+    switch (route) {
+      case SincRoute::StreamPick: hipLaunchKernelGGL((k_sinc_pipe<2, 3>), g, b, 0, s, a); break;
+      case SincRoute::StreamStereo: hipLaunchKernelGGL((k_sinc_pipe<2, 0>), g, b, 0, s, a); break;
+      default:
+        // mono: the streams with an fc < 1 tile (two waves per SIMD: all 25 constant fragments) and the end tiles, then the fc = 1
+        // streams (three per SIMD), over the same grid -- a wave of the other kind leaves behind its tile headers
+        hipLaunchKernelGGL((k_sinc_pipe<1, 2>), g, b, 0, s, a);
+        hipLaunchKernelGGL((k_sinc_pipe<1, 1>), g, b, 0, s, a);
+    }
   }
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
 }
 
-// n <= kBatchFiles files of ONE form (nch 1: mono on unit strides; nch 2: interleaved stereo) in one launch per kernel kind
-int launch_sinc_stream_batch(int device, int n, const StreamItem* items, const float4* tab, const TapModes& tmd, hipStream_t s, int nch) {
+// n <= kBatchFiles files of ONE route (StreamMono or StreamStereo) in one launch per kernel kind
+int launch_sinc_stream_batch(int device, SincRoute route, int n, const SincFile* files, const float4* tab, const TapModes& tmd, hipStream_t s) {
   if (n < 1 || n > kBatchFiles) return PAR_ERR_ARG;
   S2Batch b;
   b.n = n;
   int64_t at = 0;
   for (int k = 0; k < n; ++k) {
     b.first[k] = (int)at;
-    at += make_stream_args(device, items[k].len_out, items[k].sig, items[k].len_in, items[k].out, items[k].fa, tab, tmd, 0, b.f[k]);
+    at += make_stream_args(device, files[k], tab, tmd, 0, b.f[k]);
     if (at > INT_MAX) return PAR_ERR_ARG;
   }
   for (int k = n; k <= kBatchFiles; ++k) b.first[k] = (int)at;
   if (at <= 0) return PAR_OK;
-  if (nch == 2) {
-    hipLaunchKernelGGL((k_sinc_pipe_n<2, 0>), dim3((unsigned)at), dim3(kWave), 0, s, b);
-  } else {
-    hipLaunchKernelGGL((k_sinc_pipe_n<1, 2>), dim3((unsigned)at), dim3(kWave), 0, s, b);
-    hipLaunchKernelGGL((k_sinc_pipe_n<1, 1>), dim3((unsigned)at), dim3(kWave), 0, s, b);
+  const dim3 g((unsigned)at), w(kWave);
+  switch (route) {
+    case SincRoute::StreamStereo: hipLaunchKernelGGL((k_sinc_pipe_n<2, 0>), g, w, 0, s, b); break;
+    case SincRoute::StreamMono:
+      hipLaunchKernelGGL((k_sinc_pipe_n<1, 2>), g, w, 0, s, b);
+      hipLaunchKernelGGL((k_sinc_pipe_n<1, 1>), g, w, 0, s, b);
+      break;
+    default: return PAR_ERR_ARG;          // (StreamPick never merges)
   }
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;

@@ -2,6 +2,7 @@
 #pragma once
 #include "par_common.h"
 #include "pos_plan.h"
+#include "sinc_route.h"
 
 namespace par {
 
@@ -46,23 +47,24 @@ struct FusedArgs {
   int* redo_list;
 };
 
-// Streaming kernel (sinc2.hip): NT = 32; nch = 1: a mono signal on unit strides, nch = 2: an interleaved stereo file (sig / out
-// point at the left channel's first sample; len_in / len_out count frames); nch = 2 with pick_out_stride > 0: ONE channel of a
-// two-channel interleaved file (sig = that channel's first sample, input stride 2; outputs pick_out_stride elements apart).
-// Tiles it does not take are appended to fa.redo_list.
-struct TapModes;
-int launch_sinc_stream(int device, int64_t len_out, const float* sig, int64_t len_in, float* out, const FusedArgs& fa,
-                       const float4* tab, const TapModes& tmd, hipStream_t s, int nch, int64_t pick_out_stride = 0);
-
-// ... and several files of one form in one launch per kernel kind (k_sinc_pipe_n; at most kFusedBatchMax)
-constexpr int kFusedBatchMax = 8;
-struct StreamItem {
-  int64_t len_out;
+// One file as the streaming launches and the tile lists see it: sig / out point at the first sample of the channel (StreamStereo:
+// the left channel's; len_in / len_out count frames).  ListBatch (sinc.hip), a kernel argument, holds these: the member order stays.
+struct SincFile {
+  int64_t len_out, len_in;
   const float* sig;
-  int64_t len_in;
   float* out;
   FusedArgs fa;
 };
-int launch_sinc_stream_batch(int device, int n, const StreamItem* items, const float4* tab, const TapModes& tmd, hipStream_t s, int nch);
+
+// Streaming kernel (sinc2.hip), NT = 32, in the form the route names (sinc_route.h) -- StreamMono: a mono signal on unit strides;
+// StreamStereo: an interleaved stereo file; StreamPick: ONE channel of a two-channel interleaved file (input stride 2; outputs
+// pick_out_stride elements apart, read for this route only).  Tiles it does not take are appended to fa.redo_list.
+struct TapModes;
+int launch_sinc_stream(int device, SincRoute route, const SincFile& f, int64_t pick_out_stride, const float4* tab, const TapModes& tmd,
+                       hipStream_t s);
+
+// ... and several files of one route (StreamMono or StreamStereo) in one launch per kernel kind (k_sinc_pipe_n; at most kFusedBatchMax)
+constexpr int kFusedBatchMax = 8;
+int launch_sinc_stream_batch(int device, SincRoute route, int n, const SincFile* files, const float4* tab, const TapModes& tmd, hipStream_t s);
 
 }  // namespace par

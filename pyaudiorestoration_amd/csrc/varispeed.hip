@@ -98,27 +98,40 @@ int par_varispeed_resample_f32(int device, const double* speeds, int64_t m, cons
 
 // Fused form: no position array at all.  Needs a plan made by par_speed_to_pos_plan_fused (checkpoints + tile map
 // in `aux`); K_sinc regenerates each tile's float64 positions in LDS, bit-identical to the materialised path.
-static int varispeed_fused_impl(const char* who, int device, const double* speeds, int64_t m, const void* work, const void* aux,
-                                int64_t max_out, int64_t len_out, const float* sig, const float* sig1, int64_t sig_stride,
-                                int64_t len_in, int NT, float* out, float* out1, int64_t out_stride, void* stream, int form = -1) {
+// The argument checks of one planned file, for the three entry points.  A message starts with the entry's name, then
+// ": item <item>" for the batch's (item >= 0); it is put together only when a check fails.  The single entries come here with
+// any NT; the batch has refused a bad NT before its first item.
+static int check_fused_item(const char* entry, int item, const par_fused_item& f, int NT) {
+  char buf[80];
+  auto who = [&] {
+    if (item < 0) return entry;
+    snprintf(buf, sizeof(buf), "%s: item %d", entry, item);
+    return (const char*)buf;
+  };
+  PAR_REQUIRE(f.speeds && f.work && f.aux && f.sig0 && f.out0 && f.m >= 2, PAR_ERR_ARG, "%s: null pointer", who());
+  PAR_REQUIRE((f.sig1 == nullptr) == (f.out1 == nullptr), PAR_ERR_ARG, "%s: sig1 / out1 come together", who());
+  PAR_REQUIRE(f.len_out >= 2 && f.len_out <= f.max_out, PAR_ERR_ARG, "%s: len_out=%lld outside [2, max_out=%lld]", who(),
+              (long long)f.len_out, (long long)f.max_out);
+  PAR_REQUIRE(NT >= 1 && NT <= 512 && f.len_in >= 1 && f.sig_stride >= 1 && f.out_stride >= 1, PAR_ERR_ARG, "%s: bad sizes", who());
+  return PAR_OK;
+}
+
+static int varispeed_fused_impl(const char* who, int device, const par_fused_item& f, int NT, void* stream) {
   using namespace par;
-  PAR_REQUIRE(speeds && work && aux && sig && out && m >= 2, PAR_ERR_ARG, "%s: null pointer", who);
-  PAR_REQUIRE(len_out >= 2 && len_out <= max_out, PAR_ERR_ARG, "%s: len_out=%lld outside [2, max_out=%lld]", who,
-              (long long)len_out, (long long)max_out);
-  PAR_REQUIRE(NT >= 1 && NT <= 512 && len_in >= 1 && sig_stride >= 1 && out_stride >= 1, PAR_ERR_ARG, "%s: bad sizes", who);
+  int rc = check_fused_item(who, -1, f, NT);
+  if (rc != PAR_OK) return rc;
   PAR_HIP_CHECK(hipSetDevice(device));
   Pipe* p = nullptr;
-  int rc = get_pipe(device, &p);
+  rc = get_pipe(device, &p);
   if (rc != PAR_OK) return rc;
   hipStream_t main = as_stream(stream);
   if (p->profile) PAR_HIP_CHECK(hipEventRecord(p->t0[0], main));
-  rc = launch_sinc_fused(device, speeds, m, work, aux, max_out, len_out, sig, sig1, sig_stride, len_in, NT, out, out1,
-                         out_stride, main, form);
+  rc = launch_sinc_fused(device, f, NT, main);
   if (rc != PAR_OK) return rc;
   if (p->profile) {
     PAR_HIP_CHECK(hipEventRecord(p->t1[0], main));
     p->timed_launches = 1;
-    p->timed_samples = len_out;
+    p->timed_samples = f.len_out;
   }
   return PAR_OK;
 }
@@ -126,8 +139,8 @@ static int varispeed_fused_impl(const char* who, int device, const double* speed
 int par_varispeed_fused_f32(int device, const double* speeds, int64_t m, const void* work, const void* aux,
                             int64_t max_out, int64_t len_out, const float* sig, int64_t sig_stride, int64_t len_in,
                             int NT, float* out, int64_t out_stride, void* stream) {
-  return varispeed_fused_impl("par_varispeed_fused_f32", device, speeds, m, work, aux, max_out, len_out, sig, nullptr,
-                              sig_stride, len_in, NT, out, nullptr, out_stride, stream);
+  return varispeed_fused_impl("par_varispeed_fused_f32", device,
+                              {speeds, m, work, aux, max_out, len_out, sig, nullptr, sig_stride, len_in, out, nullptr, out_stride}, NT, stream);
 }
 
 int par_fused_redo_tiles(int device, const void* aux, int64_t max_out, int64_t m, int* tiles, void* stream) {
@@ -163,8 +176,8 @@ int par_varispeed_fused_stereo_f32(int device, const double* speeds, int64_t m, 
                                    int64_t sig_stride, int64_t len_in, int NT, float* out0, float* out1,
                                    int64_t out_stride, void* stream) {
   PAR_REQUIRE(sig1 && out1, PAR_ERR_ARG, "par_varispeed_fused_stereo_f32: null pointer");
-  return varispeed_fused_impl("par_varispeed_fused_stereo_f32", device, speeds, m, work, aux, max_out, len_out, sig0, sig1,
-                              sig_stride, len_in, NT, out0, out1, out_stride, stream);
+  return varispeed_fused_impl("par_varispeed_fused_stereo_f32", device,
+                              {speeds, m, work, aux, max_out, len_out, sig0, sig1, sig_stride, len_in, out0, out1, out_stride}, NT, stream);
 }
 
 // Several planned files in one call (r06): the K_sinc launches of files that all take the streaming kernel in one form (NT = 32;
@@ -175,18 +188,12 @@ int par_varispeed_fused_batch_f32(int device, int n_items, const par_fused_item*
   PAR_REQUIRE(n_items >= 0 && (items || n_items == 0), PAR_ERR_ARG, "par_varispeed_fused_batch_f32: null items");
   PAR_REQUIRE(NT >= 1 && NT <= 512, PAR_ERR_ARG, "par_varispeed_fused_batch_f32: NT=%d outside [1,512]", NT);
   if (n_items == 0) return PAR_OK;
-  std::vector<FusedBatchItem> v((size_t)n_items);
   for (int k = 0; k < n_items; ++k) {
-    const par_fused_item& f = items[k];
-    PAR_REQUIRE(f.speeds && f.work && f.aux && f.sig0 && f.out0 && f.m >= 2, PAR_ERR_ARG, "par_varispeed_fused_batch_f32: item %d: null pointer", k);
-    PAR_REQUIRE((f.sig1 == nullptr) == (f.out1 == nullptr), PAR_ERR_ARG, "par_varispeed_fused_batch_f32: item %d: sig1 / out1 come together", k);
-    PAR_REQUIRE(f.len_out >= 2 && f.len_out <= f.max_out, PAR_ERR_ARG, "par_varispeed_fused_batch_f32: item %d: len_out=%lld outside [2, max_out=%lld]", k,
-                (long long)f.len_out, (long long)f.max_out);
-    PAR_REQUIRE(f.len_in >= 1 && f.sig_stride >= 1 && f.out_stride >= 1, PAR_ERR_ARG, "par_varispeed_fused_batch_f32: item %d: bad sizes", k);
-    v[k] = FusedBatchItem{f.speeds, f.m, f.work, f.aux, f.max_out, f.len_out, f.sig0, f.sig1, f.sig_stride, f.len_in, f.out0, f.out1, f.out_stride};
+    const int rc = check_fused_item("par_varispeed_fused_batch_f32", k, items[k], NT);
+    if (rc != PAR_OK) return rc;
   }
   PAR_HIP_CHECK(hipSetDevice(device));
-  return launch_sinc_fused_batch(device, n_items, v.data(), NT, as_stream(stream));
+  return launch_sinc_fused_batch(device, n_items, items, NT, as_stream(stream));
 }
 
 // profiling hook for bench.py: HIP-event timing of the K_sinc launches issued by the last pipelined call

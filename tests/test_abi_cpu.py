@@ -99,6 +99,60 @@ def test_pure_host_entry_points_and_argument_errors():
     assert L.par_stft_big_scratch_bytes(n * 40, 1 << 20, 4096, 2) == 128 * (1 << 20) * 8
 
 
+def test_fused_entry_points_name_every_bad_argument():
+    """par_varispeed_fused_f32 / _stereo_f32 / _batch_f32: every argument check, its status and its full message, and the order
+    of the checks within each entry point (all of them come before any HIP call).  The single entries fold NT into "bad sizes";
+    the batch checks NT first, with a message of its own, then item after item."""
+    from pyaudiorestoration_amd import _lib
+    L = _lib.lib()
+    good = dict(speeds=8, m=4, work=8, aux=8, max_out=100, len_out=50, sig0=8, sig1=None, sig_stride=1, len_in=60, NT=32, out0=8,
+                out1=None, out_stride=1)
+    bad = [(dict(speeds=None), "null pointer"), (dict(work=None), "null pointer"), (dict(aux=None), "null pointer"),
+           (dict(sig0=None), "null pointer"), (dict(out0=None), "null pointer"), (dict(m=1), "null pointer"),
+           (dict(len_out=1), "len_out=1 outside [2, max_out=100]"), (dict(len_out=101), "len_out=101 outside [2, max_out=100]"),
+           (dict(len_in=0), "bad sizes"), (dict(sig_stride=0), "bad sizes"), (dict(out_stride=0), "bad sizes")]
+    bad_nt = [(dict(NT=0), "bad sizes"), (dict(NT=513), "bad sizes")]
+    # a null pointer is named before a bad length, a bad length before a bad size
+    order = [(dict(aux=None, len_out=1, NT=0), "null pointer"), (dict(len_out=101, sig_stride=0), "len_out=101 outside [2, max_out=100]")]
+
+    def mono(a):
+        return L.par_varispeed_fused_f32(0, a["speeds"], a["m"], a["work"], a["aux"], a["max_out"], a["len_out"], a["sig0"],
+                                         a["sig_stride"], a["len_in"], a["NT"], a["out0"], a["out_stride"], None)
+
+    def stereo(a):
+        return L.par_varispeed_fused_stereo_f32(0, a["speeds"], a["m"], a["work"], a["aux"], a["max_out"], a["len_out"], a["sig0"],
+                                                a["sig1"], a["sig_stride"], a["len_in"], a["NT"], a["out0"], a["out1"],
+                                                a["out_stride"], None)
+    for change, text in bad + bad_nt + order:
+        assert mono(dict(good, **change)) == 1 and _lib.last_error() == "par_varispeed_fused_f32: " + text, change
+    pair = dict(good, sig1=16, out1=16)
+    for change, text in bad + bad_nt + order + [(dict(sig1=None), "null pointer"), (dict(out1=None), "null pointer"),
+                                                 (dict(out1=None, len_out=1), "null pointer")]:
+        assert stereo(dict(pair, **change)) == 1 and _lib.last_error() == "par_varispeed_fused_stereo_f32: " + text, change
+
+    def batch(changes, NT=32, n=3):
+        arr = (_lib.FusedItem * n)()
+        for k, f in enumerate(arr):
+            for key, v in dict(good, **changes.get(k, {})).items():
+                if key != "NT":
+                    setattr(f, key, v)
+        return L.par_varispeed_fused_batch_f32(0, n, arr, NT, None)
+    who = "par_varispeed_fused_batch_f32: "
+    for NT in (0, 513):
+        assert batch({}, NT) == 1 and _lib.last_error() == who + f"NT={NT} outside [1,512]"
+        assert batch({0: dict(speeds=None)}, NT) == 1 and _lib.last_error() == who + f"NT={NT} outside [1,512]"      # NT first
+    assert L.par_varispeed_fused_batch_f32(0, 1, None, 0, None) == 1 and _lib.last_error() == who + "null items"      # ... after the items pointer
+    assert L.par_varispeed_fused_batch_f32(0, -1, None, 32, None) == 1 and _lib.last_error() == who + "null items"
+    together = [(dict(sig1=16), "sig1 / out1 come together"), (dict(out1=16), "sig1 / out1 come together"),
+                (dict(sig1=16, len_out=1), "sig1 / out1 come together"), (dict(sig1=16, aux=None), "null pointer")]
+    for k in (0, 2):
+        for change, text in bad + order + together:
+            assert batch({k: change}) == 1 and _lib.last_error() == who + f"item {k}: " + text, (k, change)
+    assert batch({0: dict(len_in=0), 2: dict(aux=None)}) == 1 and _lib.last_error() == who + "item 0: bad sizes"      # the first bad item
+    assert batch({1: dict(sig1=16, out1=16), 2: dict(len_out=1)}) == 1 and \
+        _lib.last_error() == who + "item 2: len_out=1 outside [2, max_out=100]"                                    # a pair is fine
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():
