@@ -6,6 +6,7 @@
 #include "pos_plan.h"
 #include "sinc_taps_gen.h"
 #include "sinc_common.h"
+#include "sinc_tap_modes.h"
 #include <atomic>
 #include <utility>
 #include <limits.h>
@@ -238,8 +239,7 @@ __device__ PAR_COLD_FN float2 sinc_slow_wave(bool want, double p, double dp, con
 //   sig[+n]*w(+n) + sig[-n]*w(-n) = R_n * ( n*(G + H) + s*(G - H) ),   G = sig[+n]*U_n,  H = sig[-n]*V_n
 // where U_n = sin(theta*(n-s)), V_n = sin(theta*(n+s)) (theta = pi*fc) are the sinc numerators.
 // The n loop runs in chunks of kChunk taps so that LDS offsets inside a chunk are instruction immediates,
-// the chunk's table entries arrive in one scalar load, and the (-1)^n sign is a free operand modifier.
-constexpr int kChunk = 4;
+// the chunk's table entries arrive in one scalar load, and the (-1)^n sign is a free operand modifier (kChunk: sinc_tap_modes.h).
 // LDS pointers carry their address space in the type so that, kept live across the chunk loop, they stay
 // ds_read base registers with immediate offsets (generic pointers degrade to flat loads, indices to a
 // shift+add per access).
@@ -270,12 +270,8 @@ __device__ __forceinline__ lds_cfloat* opaque_lds(lds_cfloat* p) {
 // error budgets (get_sinc_table: every tap pair's approximation error times its largest possible contribution,
 // summed over the pairs that use the form, stays below 3e-7 for the linear and 1.5e-6 for the constant form, against
 // the 1e-5 the reference is matched to); the table rows change meaning accordingly.
+// (kPoly2From, TapModes and the rule itself, choose_tap_modes: sinc_tap_modes.h)
 enum { kRcp = 0, kPoly2 = 1, kPoly1 = 2, kPoly0 = 3 };
-constexpr int kPoly2From = 5;     // rows n >= 5: (A_n, B_n, n, C_n) with A = win/(pi n^2), B = A/n^2, C = B/n^2
-struct TapModes {
-  int p1_from;                    // rows n >= p1_from: (A_n, B_n, n, -) linear minimax;  p1_from = 1 (mod kChunk), >= 5
-  int p0_from;                    // rows n >= p0_from: (A_n, n A_n, n, -) constant;       p0_from = 1 (mod kChunk), >= p1_from
-};
 template <int MODE>
 __device__ __forceinline__ float tap_R(float q, const float4& t) {
   if (MODE == kRcp) return fast_rcp(fmaf(q, t.y, t.x));            // row = (pi n^2/win, -pi/win, n, -)
@@ -375,13 +371,51 @@ __device__ __forceinline__ void taps_unity(const float* __restrict__ tile, const
 }
 
 // general fc in (0, 1]: numerators by 3-term recurrences seeded at the centre and run outwards.
+// In float32 the recurrence does not hold out for hundreds of taps: with fc just below 1 the rounding of c2 ~ -2 alone turns the
+// angle by 6e-8 / sin(pi dd) per step, every rounding of U is amplified by 1 / sin(theta) on its way out, and on a tone at the
+// cutoff, where the taps' errors add up, the NT = 100 loop was 2.6e-5 of the output peak off, NT = 512 2.2e-4
+// (tools/sinc_general_model.py; measured: NOTES.md, "Generic-NT tap loops").  So the numerators are re-seeded every kReseed taps
+// from the angle itself, reduced exactly:  (n -+ s) fc = n - (n dd +- h), h = fc s, hence
+//     U_n = -(-1)^n sinpi(n dd + h),   V_n = -(-1)^n sinpi(n dd - h)
+// n dd is a float32 product plus its fma remainder, so its whole part leaves without rounding.  Far out the angle needs more of
+// 1 - fc than a float32 holds (n dd ~ 280 to 1e-6 at NT = 512, fc = 0.45): ddl is the part of 1 - fc below dd -- from the float64
+// period in the position-array form, from the float32 period - 1 a wave was placed with in the fused form.
+// Every 16 taps held the contract's 1e-5 (worst 4.4e-6 of the output peak measured, 3.7e-6 modelled at NT = 378, fc = 0.99); every
+// 8 models at 1.7e-6 there, which also keeps a float32 wave within 2e-6 of a float64 one: past NT = 251 a stereo launch's waves no
+// longer stage their span and compute in float64 where a mono launch's still run these loops.
+constexpr int kReseed = 8;         // taps between two seedings (a multiple of kChunk)
 template <int R>
 struct GenState {
-  float q[R], accP[R], accM[R], U[R], Up[R], V[R], Vp[R], c2[R];
+  float q[R], accP[R], accM[R], U[R], Up[R], V[R], Vp[R], c2[R], dd[R], ddl[R], h[R];
 };
+// sinpi(hi + lo): hi a float32 product (its whole part leaves exactly), |lo| <= 1
+__device__ __forceinline__ float sinpi_reduced(float hi, float lo) {
+  const float k = rintf(hi);
+  float r = (hi - k) + lo;                   // |r| <= 1.5: fold once more
+  const float k2 = rintf(r);
+  r -= k2;
+  const float v = sinpi_half(r);
+  return (((int)k + (int)k2) & 1) ? -v : v;
+}
+// U, V at n0 (odd) and n0 - 1
+template <int R>
+__device__ __forceinline__ void general_reseed(GenState<R>& g, int n0) {
+  const float f1 = (float)n0, f0 = (float)(n0 - 1);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const float hi1 = f1 * g.dd[r], hi0 = f0 * g.dd[r];
+    const float lo1 = fmaf(f1, g.ddl[r], fmaf(f1, g.dd[r], -hi1)), lo0 = fmaf(f0, g.ddl[r], fmaf(f0, g.dd[r], -hi0));
+    g.U[r] = sinpi_reduced(hi1, lo1 + g.h[r]);
+    g.V[r] = sinpi_reduced(hi1, lo1 - g.h[r]);
+    g.Up[r] = -sinpi_reduced(hi0, lo0 + g.h[r]);
+    g.Vp[r] = -sinpi_reduced(hi0, lo0 - g.h[r]);
+  }
+}
 template <int MODE, bool LAST, int R>
 __device__ __forceinline__ void general_chunk(lds_cfloat* (&tp)[R], lds_cfloat* (&tm)[R], GenState<R>& g,
                                               const float4* __restrict__ tab, int n0, int NT) {
+  static_assert(kReseed % kChunk == 0, "seedings fall on chunk boundaries");
+  if (MODE != kRcp && ((n0 - 1) & (kReseed - 1)) == 0) general_reseed<R>(g, n0);      // (wave-uniform; the reciprocal chunk is n0 = 1)
   float4 ab[kChunk];
 #pragma unroll
   for (int k = 0; k < kChunk; ++k) ab[k] = tab[n0 + k];
@@ -421,7 +455,7 @@ __device__ __forceinline__ void general_chunk(lds_cfloat* (&tp)[R], lds_cfloat* 
 
 template <int R>
 __device__ __forceinline__ void taps_general(const float* __restrict__ tile, const int (&c)[R], const float (&s)[R],
-                                             const float (&fc)[R], const float (&dd)[R], int NT,
+                                             const float (&fc)[R], const float (&dd)[R], const float (&ddl)[R], int NT,
                                              const float4* __restrict__ tab, const TapModes tmd, float (&res)[R]) {
   GenState<R> g;
   float centre[R];
@@ -459,6 +493,9 @@ __device__ __forceinline__ void taps_general(const float* __restrict__ tile, con
     g.Up[r] = -sphi;                                  // U_0 = sin(-phi)
     g.Vp[r] = sphi;                                   // V_0 = sin(+phi)
     g.q[r] = s[r] * s[r];
+    g.dd[r] = dd[r];
+    g.ddl[r] = ddl[r];
+    g.h[r] = h;
     centre[r] = tile[c[r]] * (g.Up[r] * fast_rcp(s[r] * b0));
     g.accP[r] = g.accM[r] = 0.0f;
     tp[r] = tl + c[r] + 1;
@@ -1003,7 +1040,7 @@ __device__ PAR_COLD_FN PosDp place_exact(const double* __restrict__ speeds, cons
 // The period to the next position is 1/speed at the next step, so fc = min(1, speed_next) needs no division at all.
 __device__ __forceinline__ void place_fast(const FusedArgs& fa, long long i, long long j, long long len_out, long long anchor,
                                            double tol, int& c, float& s, float& fc, float& dd, bool& lowfc, bool& wild,
-                                           bool& exact, const bool lazy) {
+                                           bool& exact, const bool lazy, double& pm1) {
   const long long start = fa.seg_start[i];
   const SegFast sf = fa.seg_fast[i];
   const double s0 = fa.speeds[i];
@@ -1067,14 +1104,15 @@ __device__ __forceinline__ void place_fast(const FusedArgs& fa, long long i, lon
   fc = one ? 1.0f : (float)bsn;
   dd = one ? 0.0f : (float)(1.0 - bsn);
   lowfc = bsn < 0.125;
+  pm1 = one ? 0.0 : (1.0 - bsn) / bsn;                    // period - 1 in float64 (the generic tap loops' re-seeding; unused otherwise)
 }
 
 // The tap loops of one lane: NS (output, channel) slots, two at a time where the loops carry 6-10 live values per slot
 // (one pass over four spilled 48 B/lane = as much HBM write traffic as the output).  `all_unity`: fc == 1 for every lane
-// of the wave.
+// of the wave.  dls: what of 1 - fc lies below dds (the generic loops' re-seeding; zeros where the caller has no more).
 template <int NTC, int NS, int LS = 1, bool OPQ = false>
 __device__ __forceinline__ void run_taps(const float* __restrict__ tile, const int (&cs)[NS], const float (&ss)[NS],
-                                         const float (&fcs)[NS], const float (&dds)[NS], const bool all_unity,
+                                         const float (&fcs)[NS], const float (&dds)[NS], const float (&dls)[NS], const bool all_unity,
                                          const int NT, const float4* __restrict__ tab, const TapModes tmd,
                                          float (&res)[NS]) {
   static_assert(NS == 2 || NS == 4, "2 or 4 slots per lane");
@@ -1095,7 +1133,10 @@ __device__ __forceinline__ void run_taps(const float* __restrict__ tile, const i
       const float fa_[2] = {fcs[2 * h], fcs[2 * h + 1]};
       const float da[2] = {dds[2 * h], dds[2 * h + 1]};
       if constexpr (NTC > 0) taps_general_ct<NTC, 2, LS, OPQ>(tile, ca, sa, fa_, da, NT, ra);
-      else taps_general<2>(tile, ca, sa, fa_, da, NT, tab, tmd, ra);
+      else {
+        const float dl[2] = {dls[2 * h], dls[2 * h + 1]};
+        taps_general<2>(tile, ca, sa, fa_, da, dl, NT, tab, tmd, ra);
+      }
     }
     res[2 * h] = ra[0];
     res[2 * h + 1] = ra[1];
@@ -1114,7 +1155,8 @@ template <int NCH, int NTC, class SlowPos>
 __device__ __forceinline__ void sinc_tile_body(float* __restrict__ tile, int* __restrict__ red, const int t, const int64_t j0,
                                                const int64_t j_end, const long long anchor, int (&c)[kSincR / NCH],
                                                const float (&s)[kSincR / NCH], const float (&fc)[kSincR / NCH],
-                                               const float (&dd)[kSincR / NCH], const bool (&valid)[kSincR / NCH],
+                                               const float (&dd)[kSincR / NCH], const float (&ddl)[kSincR / NCH],
+                                               const bool (&valid)[kSincR / NCH],
                                                const bool (&lowfc)[kSincR / NCH], const bool unity_in, const bool wild,
                                                const float* __restrict__ sig, const float* __restrict__ sig1,
                                                const int64_t sig_stride, const int64_t len_in, const int NT,
@@ -1183,16 +1225,17 @@ __device__ __forceinline__ void sinc_tile_body(float* __restrict__ tile, int* __
   // (output, channel) slots: channel ch of an output reads the tile `ch * cap` floats further on; shift, fc and
   // 1 - fc are the SAME values for both slots of an output, so the compiler evaluates their tap weights once
   int cs[kSincR];
-  float ss[kSincR], fcs[kSincR], dds[kSincR];
+  float ss[kSincR], fcs[kSincR], dds[kSincR], dls[kSincR];
 #pragma unroll
   for (int sl = 0; sl < kSincR; ++sl) {
     cs[sl] = c[sl / NCH] + (sl % NCH) * cap;
     ss[sl] = s[sl / NCH];
     fcs[sl] = fc[sl / NCH];
     dds[sl] = dd[sl / NCH];
+    dls[sl] = ddl[sl / NCH];
     res[sl] = 0.0f;
   }
-  if (!(PAR_SINC_EXP & 1) && __any(anyfast)) run_taps<NTC, kSincR>(tile, cs, ss, fcs, dds, __all(unity), NT, tab, tmd, res);
+  if (!(PAR_SINC_EXP & 1) && __any(anyfast)) run_taps<NTC, kSincR>(tile, cs, ss, fcs, dds, dls, __all(unity), NT, tab, tmd, res);
 #pragma unroll
   for (int r = 0; r < kOut; ++r) {
     const int64_t j = j0 + t + (int64_t)r * kBlk;
@@ -1229,7 +1272,7 @@ __global__ __launch_bounds__(kSincBlock, 6) void k_sinc_pos(const double* __rest
   const long long anchor = (fabs(p0) < 4.0e18) ? (llrint(p0) & ~1ll) : 0ll;
   const double anchor_d = (double)anchor;
   int c[kSincR];
-  float s[kSincR], fc[kSincR], dd[kSincR];
+  float s[kSincR], fc[kSincR], dd[kSincR], ddl[kSincR];
   bool valid[kSincR], lowfc[kSincR];
   bool unity = true, wild = false;
 #pragma unroll
@@ -1241,17 +1284,20 @@ __global__ __launch_bounds__(kSincBlock, 6) void k_sinc_pos(const double* __rest
     s[r] = 0.25f;
     fc[r] = 1.0f;
     dd[r] = 0.0f;
+    ddl[r] = 0.0f;
     if (valid[r]) {
       const double p = pos[j];
       // last output reuses the previous period (util/resampling.py:76-77)
       const double dp = (j + 1 < len_out) ? pos[j + 1] - p : p - pos[j - 1];
       bool w;
       place_from_pos(p, dp, anchor_d, c[r], s[r], fc[r], dd[r], lowfc[r], w);
+      // the generic loops re-seed their numerators from n (1 - fc): what of 1 - fc = (dp - 1) / dp lies below the float32 dd
+      if constexpr (NTC == 0) ddl[r] = fc[r] == 1.0f ? 0.0f : (float)fma(-(double)dd[r], dp, dp - 1.0) * fc[r];
       wild = wild || w;
       unity = unity && fc[r] == 1.0f;
     }
   }
-  sinc_tile_body<1, NTC>(tile, red, t, j0, j_end, anchor, c, s, fc, dd, valid, lowfc, unity, wild, sig, (const float*)nullptr,
+  sinc_tile_body<1, NTC>(tile, red, t, j0, j_end, anchor, c, s, fc, dd, ddl, valid, lowfc, unity, wild, sig, (const float*)nullptr,
                     sig_stride, len_in, NT, tab, tmd, out, (float*)nullptr, out_stride,
                     [&](int r, double& p, double& dp) {
                       const int64_t j = j0 + t + (int64_t)r * kSincBlock;
@@ -1362,6 +1408,7 @@ __device__ __forceinline__ void fused_wave(const int64_t len_out, const float* _
   const float uf = (float)uc, u2f = uf * uf, tw1 = 2.0f * uf + 1.0f, tw0 = 2.0f * uf - 1.0f;
   int c[kOut];
   float s[kOut], ep[kOut];           // ep = max(period - 1, 0): fc = 1 / (1 + ep) and 1 - fc = ep fc are formed where the general tap path needs them
+  float epl[kOut] = {};              // generic tap loops: what of period - 1 lies below ep, where placement knew it in float64 (redone outputs)
   bool valid[kOut], lowfc[kOut], redo[kOut], slow[kOut], second[kOut], last[kOut];
   bool unity = true, wild = (hd.flags & 1) != 0, anyredo = false, anysecond = false, anycubic = false;
   int Irel[kOut];
@@ -1444,13 +1491,18 @@ __device__ __forceinline__ void fused_wave(const int64_t len_out, const float* _
         while (i + 1 < fa.nseg && fa.seg_start[i + 1] <= j) ++i;
         bool ex = !slow[r], w = false;
         float fcr = 1.0f, ddr = 0.0f;
+        double pm1 = 0.0;
         // (lazy plans: near-ties go through place_fast too -- it settles all but 1 in 10^4 of them without the walk)
-        if (slow[r] || lazy) place_fast(fa, i, j, len_out, anchor, tol, c[r], s[r], fcr, ddr, lowfc[r], w, ex, lazy);
+        if (slow[r] || lazy) place_fast(fa, i, j, len_out, anchor, tol, c[r], s[r], fcr, ddr, lowfc[r], w, ex, lazy, pm1);
         if (ex) {
           const PosDp e = place_exact(fa.speeds, fa.seg_start, fa.seg_off, lazy ? nullptr : fa.ck, i, j, len_out);
           place_from_pos(e.p, e.dp, (double)anchor, c[r], s[r], fcr, ddr, lowfc[r], w);
+          pm1 = e.dp > 1.0 ? e.dp - 1.0 : 0.0;
         }
         ep[r] = ddr / fcr;                                 // (1 - fc) / fc = period - 1 (0 when fc == 1)
+        // every output of a piece outside the record model (any period beyond 1/32 of 1) comes through here: far out the
+        // generic loops need more of the period than this float32 quotient holds (n (1 - fc) = 265 at NT = 379, fc = 0.3)
+        if constexpr (NTC == 0) epl[r] = ep[r] > 0.0f ? (float)(pm1 - (double)ep[r]) : 0.0f;
         wild = wild || w;
       }
     }
@@ -1541,6 +1593,7 @@ __device__ __forceinline__ void fused_wave(const int64_t len_out, const float* _
   // 1 - fc are the SAME values for both slots of an output, so the compiler evaluates their tap weights once
   int cs[NS];
   float ss[NS], eps[NS], res[NS];
+  float dls[NS] = {};                // what of 1 - fc lies below dds: the generic loops' re-seeding (run_taps)
 #pragma unroll
   for (int sl = 0; sl < NS; ++sl) {
     cs[sl] = c[sl / NCH] * LS + (sl % NCH) * CHO;
@@ -1580,8 +1633,15 @@ __device__ __forceinline__ void fused_wave(const int64_t len_out, const float* _
     for (int sl = 0; sl < NS; ++sl) {
       fcs[sl] = fast_rcp(1.0f + eps[sl]);
       dds[sl] = eps[sl] * fcs[sl];
+      // 1 - fc = x / (1 + x) for the period - 1 = x = eps + epl the output was placed with; dds is off it by the reciprocal's
+      // ulp and its own rounding, n times that at tap n: the short last wave of a file stages NT = 378 at fc = 0.3, n dds = 265
+      // (d(1 - fc) / dx = fc^2 takes epl along)
+      if constexpr (NTC == 0) {
+        const float lo = (HOT || valid[sl / NCH]) ? epl[sl / NCH] * fcs[sl] : 0.0f;
+        dls[sl] = fmaf((float)fma(-(double)dds[sl], 1.0 + (double)eps[sl], (double)eps[sl]), fcs[sl], lo * fcs[sl]);
+      }
     }
-    run_taps<NTC, NS, LS, fused_is_farrow(NCH, NTC, NS)>(tile, cs, ss, fcs, dds, __all(unity), NT, tab, tmd, res);
+    run_taps<NTC, NS, LS, fused_is_farrow(NCH, NTC, NS)>(tile, cs, ss, fcs, dds, dls, __all(unity), NT, tab, tmd, res);
   }
 #if PAR_SINC_EXP & 128
   {                                   // the tap loops a second time (what does ONE more pass cost?)
@@ -1594,7 +1654,7 @@ __device__ __forceinline__ void fused_wave(const int64_t len_out, const float* _
       fcs[sl] = fast_rcp(1.0f + eps[sl]);
       dds[sl] = eps[sl] * fcs[sl];
     }
-    if (__any(anyfast)) run_taps<NTC, NS, LS, fused_is_farrow(NCH, NTC, NS)>(tile, cs, ss, fcs, dds, __all(unity), NT, tab, tmd, res2);
+    if (__any(anyfast)) run_taps<NTC, NS, LS, fused_is_farrow(NCH, NTC, NS)>(tile, cs, ss, fcs, dds, dls, __all(unity), NT, tab, tmd, res2);
 #pragma unroll
     for (int sl = 0; sl < NS; ++sl) res[sl] += 1e-9f * res2[sl];
   }
