@@ -186,12 +186,16 @@ __device__ __forceinline__ int clamp64(int n) { return n < 0 ? 0 : (n > 64 ? 64 
 __device__ __forceinline__ unsigned long long prefix(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }   // 0 <= n <= 64
 
 // Placement of one row (64 consecutive outputs, lane l) from its block records (pos_plan.h BlockRec): window centre relative
-// to A0, sub-sample shift, max(period - 1, 0); `bad` = the lane's block leaves the plain record model (a slow piece, the cubic
-// term) or its centre lies within the reference's own rounding of a tie -- such tiles go to the block kernel.
+// to A0, sub-sample shift, max(period - 1, 0); bad() = the lane's block leaves the plain record model (a slow piece, the cubic
+// term: flags of its record word m) or its centre lies within the reference's own rounding of a tie -- such tiles go to the block
+// kernel.  The word and the tie test leave separately: the loop ORs the two rows' words and tests the flags once (r10).
+constexpr unsigned kRecBadFlags = kRecSlow0 | kRecSlow1 | kRecCubic;
 struct S2Row {
   int c;
   float s, ep;
-  bool bad;
+  unsigned m;
+  bool tie;
+  __device__ __forceinline__ bool bad() const { return (m & kRecBadFlags) != 0u || tie; }
 };
 template <bool SECOND = true>                    // false: the caller knows that no lane of the row takes its block's second piece
 __device__ __forceinline__ S2Row s2_place_row(const uint4 ra, const uint4 rb, const int u, const int cbase, const float uf,
@@ -209,7 +213,8 @@ __device__ __forceinline__ S2Row s2_place_row(const uint4 ra, const uint4 rb, co
   o.s = frac - ri;
   o.c = cbase + irel + (int)ri;
   o.ep = __builtin_amdgcn_fmed3f(e, 0.0f, 3.0e38f);             // max(e, 0) in one instruction
-  o.bad = (m & (kRecSlow0 | kRecSlow1 | kRecCubic)) != 0u || !(fabsf(fabsf(o.s) - 0.5f) > tolf);
+  o.m = m;
+  o.tie = !(fabsf(fabsf(o.s) - 0.5f) > tolf);                   // (two compares per pass: a float minimum of the rows would drop a NaN)
   return o;
 }
 
@@ -233,14 +238,17 @@ __device__ __forceinline__ S2Row s2_place_row(const uint4 ra, const uint4 rb, co
 //     wait vmcnt + fence
 //     READS    the records of PLACE(k + 1), CONV's ring chunk, the gathers of OUT(k) (3 rows + 5 ring samples per output):
 //              their addresses are loop state, the data landed before the fence
-//     PLACE(k + 1) behind a partial lgkmcnt (the records alone); the loop's exit test (scalar) rides beside it
+//     PLACE(k + 1) behind a partial lgkmcnt (the records alone); the loop's exit margin -- scalar instructions only, every
+//              minimum pinned to a scalar register (r10) -- rides beside it.  Seven passes in eight lie inside one tile and
+//              take both rows' anchor from one add; the pass that straddles a tile border selects per lane in a block of
+//              its own, behind a scalar branch and out of the loop's line
 //     READS    BANK(k + 1)'s six image fragments, as soon as ws is known
 //     OUT(k)   arithmetic, pinned here: the fragments land under it -- both rows in the fc = 1 and the order-6 loop; in the
 //              order-5 loop (the benchmark's fc < 1 passes) the first row only
 //     BANK(k + 1) MFMAs -- order 5: OUT(k)'s second row dealt out behind them, two vector instructions to an MFMA (which hides
 //              that many) -- then the row writes (behind OUT(k)'s gathers); CONV arithmetic + image writes (behind the
 //              fragment reads)
-//     FETCH, DMA, stores, fence
+//     FETCH, DMA, stores (one 32-bit byte offset per pass off the stream's scalar base, row 1 as the instruction offset), fence
 // Same hazards as above -- nothing read that the iteration wrote, gathers before row writes, fragment reads before image writes,
 // one fence, one vmcnt wait -- and the same arithmetic expressions: the outputs are bit-identical to the r06 order's (NOTES r08).
 // (tools/isa_census.py --waits lists each read, the wait that covers it and the wave's own vector work in between.)
@@ -284,7 +292,8 @@ static_assert(sizeof(S3LdsUnity) <= 10240 && offsetof(S3LdsUnity, recs) % 16 == 
               "sixteen fc = 1 streams per compute unit");
 
 struct S3Pass {                                  // a placed pass: 128 candidate outputs j .. j + 127 (two per lane)
-  int c[2];                                      // window centre relative to A0
+  int cw[2];                                     // window centre relative to ws: the row's bank slot before its clamp to 0 .. 127 (r10: what
+                                                 // the placement's nok test works out and OUT uses; the centre itself has no other reader)
   float s[2], ep[2];                             // shift, max(period - 1, 0)
   int nok[2];                                    // lanes of row r the pass finishes: l < nok[r]   (wave-uniform)
   int j, ws;                                     // first output (relative to Ja), first bank centre (wave-uniform)
@@ -467,8 +476,10 @@ __device__ __forceinline__ float s3_out_row(const LDS& L, const int ci, const fl
 // algebra in every iteration).
 __device__ __forceinline__ unsigned long long s3_convert_verdict(const float x0, const float x1) {
   const float am = fmaxf(fabsf(x0), fabsf(x1));
-  const unsigned long long big = __ballot(!(fabsf(x0) < kImgMax) || !(fabsf(x1) < kImgMax));       // (also set for NaN)
-  const unsigned long long loud = __ballot(am >= kQuiet), some = __ballot(am > 0.0f);
+  // (each ballot straight from ONE compare, the masks combined on the scalar unit: a ballot of `a || b` went through a bool in a
+  // vector register -- v_cndmask 0, 1 and a compare with 0 again -- in k_sinc_pipe<1, 1>, r10)
+  const unsigned long long big = __builtin_amdgcn_ballot_w64(!(fabsf(x0) < kImgMax)) | __builtin_amdgcn_ballot_w64(!(fabsf(x1) < kImgMax));       // (also set for NaN)
+  const unsigned long long loud = __builtin_amdgcn_ballot_w64(am >= kQuiet), some = __builtin_amdgcn_ballot_w64(am > 0.0f);
   return big | (loud == 0ull ? some : 0ull);
 }
 template <int NCH, class LDS, class V>
@@ -706,6 +717,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
   int tc_tend = 0, tc_dA0 = 0, tc_dA1 = 0, tc_fl0 = 0, tc_fl1 = 0, tc_flm = 0;
   struct PlaceRecs {
     uint4 ra0, rb0, ra1, rb1;                    // first / second pieces of the blocks of the lane's two outputs
+    int t5;                                      // (j & 31) + l, which named them: the placement takes it from here
   };
   // (rbytes: the record buffer as its byte offset in L.recs; jb = (j >> kRecShift) - rb, the pass's first block in the buffer --
   // the loop's exit test needs it too, so the loop works it out once)
@@ -713,7 +725,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     const int t5 = (j & (kRec - 1)) + l;
     const int bi = (jb + (t5 >> kRecShift)) & 7;
     const uint4* rp = &L.recs[0][0] + (rbytes >> 4);
-    return PlaceRecs{rp[bi], rp[8 + bi], rp[(bi + 2) & 7], rp[8 + ((bi + 2) & 7)]};
+    return PlaceRecs{rp[bi], rp[8 + bi], rp[(bi + 2) & 7], rp[8 + ((bi + 2) & 7)], t5};
   };
   // (EARLY: the records were read ahead by place_load; otherwise they are read here, where the compiler keeps the second pieces'
   // reads inside the variant that selects them)
@@ -732,28 +744,39 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     const int dA0 = tc_dA0, dA1 = tc_dA1;
     P.fl0 = tc_fl0;
     P.fl1 = tc_fl1;
-    const int t5 = (j & (kRec - 1)) + l;
-    const int u = t5 & (kRec - 1);
     uint4 ra0, rb0, ra1, rb1;
+    int t5;
     if constexpr (decltype(early)::value) {
-      ra0 = RR.ra0, rb0 = RR.rb0, ra1 = RR.ra1, rb1 = RR.rb1;
+      ra0 = RR.ra0, rb0 = RR.rb0, ra1 = RR.ra1, rb1 = RR.rb1, t5 = RR.t5;
     } else {
+      t5 = (j & (kRec - 1)) + l;
       const int bi = (jb + (t5 >> kRecShift)) & 7;
       const uint4* rp = &L.recs[0][0] + (rbytes >> 4);
       ra0 = rp[bi], rb0 = rp[8 + bi], ra1 = rp[(bi + 2) & 7], rb1 = rp[8 + ((bi + 2) & 7)];
     }
+    const int u = t5 & (kRec - 1);
     const int uc = u - kRec / 2;
     const float uf = (float)uc, u2f = uf * uf, tw1 = fmaf(2.0f, uf, 1.0f), tw0 = tw1 - 2.0f;
     // lanes of the two rows that lie in the tile of j: l < nt[r] (a lane's compare needs no clamp; the cold path's masks clamp)
     P.nt[0] = P.tend - j;
     P.nt[1] = P.tend - j - 64;
+    // The rows' tile anchors.  Seven passes in eight lie inside the tile of j (a scalar test): both rows count from its anchor.
+    // The pass that straddles a tile border selects per lane, behind a scalar BRANCH (the wave barrier -- no instruction -- keeps
+    // the compiler from folding the test into the lanes' selects again, as in s3_ring_mirrors): as a select alone every pass
+    // paid two copies of the anchors into vector registers, a compare and a select per row (r10).
+    int cb0 = dA0 + uc, cb1 = cb0;
+    if (__builtin_expect(P.nt[0] < kPass, 0)) {
+      __builtin_amdgcn_wave_barrier();
+      cb0 = (l < P.nt[0] ? dA0 : dA1) + uc;
+      cb1 = (l < P.nt[1] ? dA0 : dA1) + uc;
+    }
     // a segment starts inside one block in eight: most passes have no second piece to select
     if (__ballot((unsigned)u > (ra0.x & 31u) || (unsigned)u > (ra1.x & 31u)) == 0ull) {
-      P.R[0] = s2_place_row<false>(ra0, rb0, u, (l < P.nt[0] ? dA0 : dA1) + uc, uf, u2f, tw1, tw0, tolf);
-      P.R[1] = s2_place_row<false>(ra1, rb1, u, (l < P.nt[1] ? dA0 : dA1) + uc, uf, u2f, tw1, tw0, tolf);
+      P.R[0] = s2_place_row<false>(ra0, rb0, u, cb0, uf, u2f, tw1, tw0, tolf);
+      P.R[1] = s2_place_row<false>(ra1, rb1, u, cb1, uf, u2f, tw1, tw0, tolf);
     } else {
-      P.R[0] = s2_place_row(ra0, rb0, u, (l < P.nt[0] ? dA0 : dA1) + uc, uf, u2f, tw1, tw0, tolf);
-      P.R[1] = s2_place_row(ra1, rb1, u, (l < P.nt[1] ? dA0 : dA1) + uc, uf, u2f, tw1, tw0, tolf);
+      P.R[0] = s2_place_row(ra0, rb0, u, cb0, uf, u2f, tw1, tw0, tolf);
+      P.R[1] = s2_place_row(ra1, rb1, u, cb1, uf, u2f, tw1, tw0, tolf);
     }
     // (one integer maximum serves the regime test and the moment correction's limit: two compares where there were a float
     // maximum with its quieting moves and three; ep is fmed3(e, 0, 3e38): never NaN, -0 sorts below everything)
@@ -767,7 +790,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
   S3Pass P;                                      // the pass OUT works on next (placed, its bank in LDS)
   P.nok[0] = P.nok[1] = 0;
   P.j = P.ws = 0;
-  P.c[0] = P.c[1] = 0;
+  P.cw[0] = P.cw[1] = 0;
   P.s[0] = P.s[1] = P.ep[0] = P.ep[1] = 0.0f;
 
   auto out_pass = [&](auto mode_tag, const S3Pass& Q, float (&res)[2], const int ch = 0) {
@@ -775,7 +798,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
     const int wsK = Q.ws - wbase;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-      int ci = Q.c[r] - Q.ws;
+      int ci = Q.cw[r];
       ci = ci < 0 ? 0 : (ci > kPass - 1 ? kPass - 1 : ci);
       float sr = Q.s[r], epr = Q.ep[r];
 #if !PAR_S3_SHARE_OUT
@@ -786,19 +809,25 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       res[r] = s3_out_row<MODE, NCH>(L, ci, sr, epr, wsK, ch);
     }
   };
+  // The unit-stride stores: ONE 32-bit byte offset per pass, (j + l) elements, off the stream's scalar base outW; row 1 is the
+  // instruction offset 64 elements further on.  (Indexed as outW[j + 64 r + l] every row's address was widened to 64 bits in
+  // vector registers, r10.)  The strided one-channel form keeps its 64-bit index.
+  static_assert(48ull * kSincTileOutputs * sizeof(float2) + 2 * kWave * sizeof(float2) < (1ull << 32),
+                "the largest stream (48 tiles of stereo frames) stays below 2^32 bytes");
+  auto out_bytes = [&](auto elem, int j) -> size_t { return (size_t)(((unsigned)j + (unsigned)l) * (unsigned)sizeof(elem)); };
   auto store_pass = [&](const S3Pass& Q, const float (&res)[2]) {
 #pragma unroll
     for (int r = 0; r < 2; ++r)
       if (l < Q.nok[r] && !(PAR_S2_EXP & 4)) {
         if constexpr (kPick) outW[(int64_t)((unsigned)Q.j + 64u * r + (unsigned)l) * a.out_stride] = res[r];
-        else outW[(unsigned)Q.j + 64u * r + (unsigned)l] = res[r];
+        else *reinterpret_cast<float*>(reinterpret_cast<char*>(outW) + out_bytes(float{}, Q.j) + kWave * sizeof(float) * r) = res[r];
       }
   };
   auto store_pass2 = [&](const S3Pass& Q, const float (&res0)[2], const float (&res1)[2]) {      // stereo: a frame per lane and row
 #pragma unroll
     for (int r = 0; r < 2; ++r)
       if (l < Q.nok[r] && !(PAR_S2_EXP & 4))
-        reinterpret_cast<float2*>(outW)[(unsigned)Q.j + 64u * r + (unsigned)l] = make_float2(res0[r], res1[r]);
+        *reinterpret_cast<float2*>(reinterpret_cast<char*>(outW) + out_bytes(float2{}, Q.j) + kWave * sizeof(float2) * r) = make_float2(res0[r], res1[r]);
   };
   // one chunk of the ring -> float16 image(s); stereo: both channels of the chunk
   // (w0 = 128 x chunk; returns the lane mask of s3_convert_verdict: zero when the chunk suits float16)
@@ -837,8 +866,8 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       // lane sets: valid lanes (inside the range), lanes of this tile
       int nv[2] = {clamp64(nJ - j0), clamp64(nJ - j0 - 64)};
       // the moment correction covers 1 - fc <= 0.0125
-      const unsigned long long b0 = __ballot(Q.R[0].bad || !(Q.R[0].ep <= kEpMaxMom)) & prefix(nv[0]),
-                               b1 = __ballot(Q.R[1].bad || !(Q.R[1].ep <= kEpMaxMom)) & prefix(nv[1]);
+      const unsigned long long b0 = __ballot(Q.R[0].bad() || !(Q.R[0].ep <= kEpMaxMom)) & prefix(nv[0]),
+                               b1 = __ballot(Q.R[1].bad() || !(Q.R[1].ep <= kEpMaxMom)) & prefix(nv[1]);
       const int nt0 = clamp64(Q.nt[0]), nt1 = clamp64(Q.nt[1]);
       const unsigned long long bad_here = (b0 & prefix(nt0)) | (b1 & prefix(nt1));
       const bool bad_next = ((b0 & ~prefix(nt0)) | (b1 & ~prefix(nt1)) | (unsigned long long)((Q.fl1 & 1) && tend < nJ)) != 0ull;
@@ -852,10 +881,10 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       S3Pass N;
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
-        N.c[r] = Q.R[r].c;
+        N.cw[r] = Q.R[r].c - ws;
         N.s[r] = Q.R[r].s;
         N.ep[r] = Q.R[r].ep;
-        const unsigned long long in = __ballot(Q.R[r].c - ws < kPass);
+        const unsigned long long in = __ballot(N.cw[r] < kPass);
         N.nok[r] = __popcll(in & prefix(nv[r]));
       }
       N.j = j0;
@@ -1021,17 +1050,17 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       //         (no flapping between the two; such a lane has fc < 1).
       constexpr int kEpGen = 0x33800000;          // 2^-24
       const int ep_hi = MODE == 1 ? kEpGen : (MODE == 2 ? __float_as_int(kEpMom5) : __float_as_int(kEpMaxMom));
-      const int n_none = __popcll(__ballot(Q.R[0].bad || Q.R[1].bad || Q.epm > ep_hi));
+      const int n_none = __popcll(__ballot(((Q.R[0].m | Q.R[1].m) & kRecBadFlags) != 0u || Q.R[0].tie || Q.R[1].tie || Q.epm > ep_hi));
       int n_some = 1;
       if constexpr (MODE == 2) n_some = __popcll(__ballot(Q.epm > kEpGen));
       if constexpr (MODE == 3) n_some = __popcll(__ballot(Q.epm > __float_as_int(kEpMom5Lo)));
       const int ws = __builtin_amdgcn_readfirstlane(Q.R[0].c) & ~7;
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
-        N.c[r] = Q.R[r].c;
+        N.cw[r] = Q.R[r].c - ws;
         N.s[r] = Q.R[r].s;
         N.ep[r] = Q.R[r].ep;
-        N.nok[r] = __popcll(__ballot(Q.R[r].c - ws < kPass));
+        N.nok[r] = __popcll(__ballot(N.cw[r] < kPass));
       }
       N.j = j0;
       N.ws = ws;
@@ -1041,13 +1070,21 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       // 161 <= d <= 473; the next chunk to convert came from the file; the records' guess held
       // (the masks enter as lane COUNTS: a select on `mask == 0` is compiled as 64-bit mask algebra and a vector select.  A pass
       // finishes <= 128 outputs, so 16 x n_none sinks that margin below zero whatever the pass finishes)
+      // (every term is wave-uniform, and every minimum is pinned to a scalar register where it is formed -- no instruction: left
+      // alone the compiler folds min(min(a, b), c) into min3, which only the vector unit has, and the chain's tail ran there from
+      // copies of its scalar terms, r10)
+      auto smin = [](int x, int y) {
+        int r = min(x, y);
+        asm volatile("" : "+s"(r));
+        return r;
+      };
       adv = N.nok[0] + N.nok[1];
-      m = min(tc_flm, nJm - j0);
-      m = min(m, adv - 120 - 16 * n_none);
-      m = min(m, min(d - 161, 473 - d));
-      m = min(m, cn_lim - w0);
-      m = min(m, min(jb, 1 - jb));
-      if constexpr (MODE != 1) m = min(m, n_some - 1);
+      m = smin(tc_flm, nJm - j0);
+      m = smin(m, adv - 120 - 16 * n_none);
+      m = smin(m, smin(d - 161, 473 - d));
+      m = smin(m, cn_lim - w0);
+      m = smin(m, smin(jb, 1 - jb));
+      if constexpr (MODE != 1) m = smin(m, n_some - 1);
       };
       float res[2];
       if constexpr (kEarly) {
@@ -1059,7 +1096,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         const int wsP = P.ws - wbase;
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-          int ci = P.c[r] - P.ws;
+          int ci = P.cw[r];
           ci = ci < 0 ? 0 : (ci > kPass - 1 ? kPass - 1 : ci);
           G[r] = s3_out_load<MODE, NCH>(L, ci, wsP);
         }
@@ -1102,11 +1139,8 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
           bank_math<MODE != 1, MODE == 3>(L, fr, fmr, X, l);
         }
         // CONV's arithmetic and image writes (behind the fragment reads), then FETCH and the stores: five memory operations, in
-        // this order
-        // (left alone the loop's exit test sinks behind the stores, where the wave offers the vector port nothing: worked out
-        // here, beside the matrix work)
-        m = __builtin_amdgcn_readfirstlane(m);
-        asm volatile("" : "+s"(m));
+        // this order.  (The loop's exit margin is scalar work since r10 -- formed in place_next, min by min -- and needs no place
+        // beside the matrix work: until then its tail ran on the vector port and was pinned here.)
         cok = s3_convert_math(L, w0, l, cxx);
         fetch_records_at(rbytes ^ (2 * kRecBufBytes), rbC);
         chunk_dma_at(w0 < dn_lim, dsrc, dslot);
