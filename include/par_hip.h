@@ -766,6 +766,46 @@ int par_stft_track_peak_f64(int device, const float* x, int64_t n, int64_t x_str
  * into zero sections raises), avg_pitch below the longest cycle: PAR_ERR_ARG before any device call. */
 int par_cycle_fold_f64(int device, const double* v, int64_t count, int p_first, int n_cand, double* avg, int64_t avg_pitch,
                        double* delta, void* stream);
+/* ---- MaxMono dropout repair (dropouts_gui.py:137-163): per STFT bin the louder (max) or the quieter (min) of two channels --------
+ * par_select_spectrum_f32, par_maxmono_stft_f32, par_maxmono_stft_supported and par_maxmono_stft_transformed_frames are added at
+ * ABI 109: par_version() stays 109.  All work on the caller's stream, none synchronises the host.
+ *
+ * par_select_spectrum_f32: specL, specR (DEVICE c64 [n_frames][pitch], the layout par_stft_f32 mode 0 writes; pitch 0 = bins) ->
+ *   out_max = where(|L| > |R|, L, R), out_min = where(|L| < |R|, L, R), same layout, padding cells untouched.
+ * |.| is the float32 value numpy's np.abs gives for complex64 (see par_gate_spectrum_f32).  On a tie both outputs take R, and
+ * where a magnitude is NaN both comparisons are false, so again both take R.  The result is the selected input's bits: nothing
+ * is multiplied, so NaN payloads, -0.0 and denormals pass through, and it equals numpy's np.where on the same spectra bit for
+ * bit.  Either output may be NULL (not both).  Outputs must not overlap the inputs or each other.  Null inputs, both outputs
+ * NULL, n_frames < 0, bins < 1, pitch < bins, overlapping ranges: PAR_ERR_ARG before any device call.  n_frames == 0: PAR_OK. */
+int par_select_spectrum_f32(int device, const float* specL, const float* specR, int64_t n_frames, int64_t bins, int64_t pitch,
+                            float* out_max, float* out_min, void* stream);
+/* Fused MaxMono, one launch: the channel views xL[i * x_stride] and xR[i * x_stride] (DEVICE f32, i < n; the two columns of an
+ * interleaved file for instance) are each zero-extended to n + n_fft/2 (fix_length) and transformed (`window` DEVICE f32[n_fft];
+ * reflect padding of the extended length, frames and scaling of par_stft_f32 mode 0), selected bin by bin as
+ * par_select_spectrum_f32 does, and the max and the min spectrum are inverse transformed and overlap-added with the
+ * window-sum-square normalisation of par_istft_f32 (length n) into y_max[i * ymax_stride] and y_min[i * ymin_stride] (DEVICE f32).
+ * No spectrogram reaches HBM.  y_max or y_min may be NULL (not both); that inverse is then skipped.  Contract: bin k
+ * holds the decision par_select_spectrum_f32 makes on par_stft_f32's spectra of the two channels, except that it may hold
+ * either channel where the two magnitudes differ by no more than 2^-21 (|L[k]| + |L[H-k]| + |R[k]| + |R[H-k]|), H = n_fft/2
+ * (16 float32 ulps where the four are alike): a last-bit change of the packed transform's cells k and H - k moves a bin by
+ * up to 2^-22 of that sum.  tests/test_maxmono_gpu.py holds the kernel to this.  The forward path is K_stft
+ * mode 0's, operation by operation in the source, but the compiler contracts one complex multiply of the last transform stage
+ * into a different fused multiply-add in the two kernels, so a part of a bin can differ from par_stft_f32's in its last
+ * bit.  Measured: 2 bins of 2.1e8 on a 10-min stereo file at 2048/128 decided differently (5.3e-5 of the peak over one
+ * frame's reach each), none at 512/64 and 2048/512 (NOTES.md, MaxMono).  Ties by construction (xR = -xL, xR = xL) are exact in
+ * both.  Fused sizes: n_fft a power of two in
+ * [16, 8192] and 1 <= hop <= n_fft, as far as the frames, two overlap-add rings of n_fft + Frames * hop floats (Frames =
+ * max(1, 4096 / n_fft) frames per round) and hop floats of window sums fit 160 KB of LDS: every hop up to n_fft = 4096, and
+ * hop <= 5114 at n_fft = 8192 (par_maxmono_stft_supported says so without a device).  Everything else returns
+ * PAR_ERR_UNSUPPORTED with the outputs untouched (compose par_stft_f32, par_select_spectrum_f32 and par_istft_f32).  Null
+ * pointers, n < 1, hop < 1, a stride < 1: PAR_ERR_ARG; all before any device call. */
+int par_maxmono_stft_f32(int device, const float* xL, const float* xR, int64_t n, int64_t x_stride, int n_fft, int hop,
+                         const float* window, float* y_max, int64_t ymax_stride, float* y_min, int64_t ymin_stride, void* stream);
+/* 1 when par_maxmono_stft_f32 takes (n_fft, hop), else 0 (host arithmetic) */
+int par_maxmono_stft_supported(int n_fft, int hop);
+/* Frames par_maxmono_stft_f32 transforms per channel (host only, for reporting the streaming form's redundant-frame share);
+ * 0 when the size is unsupported. */
+int64_t par_maxmono_stft_transformed_frames(int64_t n, int n_fft, int hop);
 #ifdef __cplusplus
 }
 #endif

@@ -246,7 +246,25 @@ def parser():
     k.add_argument("--json", default=None, metavar="REPORT.json", help="write the figures (a list when several files are given)")
     k.add_argument("--resample", action="store_true", help="remove the measured cycle: <stem>_res.wav through the sinc resampler")
     k.add_argument("--quality", type=int, default=50, help="sinc_quality (NT) of --resample")
+    x = sub.add_parser("maxmono", help="MaxMono dropout repair of a two-track transfer: per STFT bin the louder channel -> <stem>max.wav, "
+                                       "the quieter -> <stem>min.wav")
+    x.add_argument("files", nargs="+")
+    x.add_argument("--fft", type=int, default=512, help="FFT size")
+    x.add_argument("--overlap", type=int, default=4, help="hop = fft / overlap")
     return ap
+
+
+def _maxmono(args):
+    from . import dropouts
+    failed = 0
+    for path in args.files:
+        try:
+            for p in dropouts.process(path, args.fft, args.overlap):
+                logging.info("wrote %s", p)
+        except Exception:                               # keep the other files going, as the GUI does
+            logging.exception(f"{path} failed")
+            failed += 1
+    return 1 if failed else 0
 
 
 def _difeq(args):
@@ -338,6 +356,8 @@ def main(argv=None):
         return _difeq(args)
     if args.cmd == "cyclic":                    # file after file, one GPU
         return _cyclic(args)
+    if args.cmd == "maxmono":                   # file after file, one GPU
+        return _maxmono(args)
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()
     for f in sorted(args.files, key=lambda p: -os.path.getsize(p)):     # longest first

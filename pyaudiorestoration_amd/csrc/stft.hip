@@ -2092,6 +2092,263 @@ __global__ __launch_bounds__(FftGeom<LOGH>::Threads, GateGeom<LOGH>::kWaves) voi
   }
 }
 
+// ---- MaxMono dropout repair (dropouts_gui.py:137-163, added at ABI 109) ------------------------------------------------------------
+// D_max = where(|D_L| > |D_R|, D_L, D_R), D_min = where(|D_L| < |D_R|, D_L, D_R): a tie and a NaN magnitude give D_R in both.
+// The magnitudes are numpy's complex64 np.abs (np_abs.h); the selection copies the chosen bin's bits, it multiplies nothing.
+__device__ __forceinline__ void select_bin(float2 l, float2 r, float2& mx, float2& mn) {
+  const float ml = np_abs_c64(l.x, l.y), mr = np_abs_c64(r.x, r.y);
+  mx = ml > mr ? l : r;
+  mn = ml < mr ? l : r;
+}
+
+__global__ __launch_bounds__(256) void k_select_spectrum(const float2* __restrict__ specL, const float2* __restrict__ specR,
+                                                         int64_t n_frames, int64_t bins, int64_t pitch, float2* __restrict__ out_max,
+                                                         float2* __restrict__ out_min) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= bins) return;
+  for (int64_t f = blockIdx.y; f < n_frames; f += gridDim.y) {
+    float2 mx, mn;
+    select_bin(specL[f * pitch + b], specR[f * pitch + b], mx, mn);
+    if (out_max) out_max[f * pitch + b] = mx;
+    if (out_min) out_min[f * pitch + b] = mn;
+  }
+}
+
+// Fused MaxMono: the two-channel, two-output sibling of k_gate_stft, with its runs, rounds and fix_length / reflect gather.
+// Order of a round over ONE frame buffer: L forward -> the lane keeps L's bin pairs (k, H - k) in registers -> R forward ->
+// select in registers -> the inverse input of the max spectrum goes to the frame, that of the min spectrum stays in registers
+// -> max inverse, overlap-add into ring 0 -> min inverse input to the frame -> min inverse, overlap-add into ring 1 -> both
+// rings' completed positions are normalised, stored and cleared.  The rings are exactly 2H + Frames * hop floats (not rounded
+// to a power of two: at 8192 points two rounded rings alone would be 128 KB): a position's slot is its distance from the
+// run's first sample modulo the ring, kept as one running base per round and a conditional subtract per position.
+template <int LOGH>
+struct MaxMonoGeom {
+  using G = FftGeom<LOGH>;
+  static int rounds(int s) { return GateGeom<LOGH>::rounds(s); }
+  static int ring(int hop) { return 2 * G::H + G::Frames * hop; }
+  static size_t lds(int hop) { return G::FramesLds + (size_t)(2 * ring(hop) + hop) * sizeof(float); }
+  // Waves per SIMD the register allocation must keep: two at every size (K_maxmono, has the figures).  The second
+  // channel's bin pairs and the second inverse input do not fit the 168 VGPRs of three waves: asked for three, every size from
+  // 32 points up spilled 128-372 bytes per lane and ran slower (10-min stereo: 2048/512 1.69 against 1.60 ms, 2048/128 5.83
+  // against 5.50, 512/64 2.00 against 1.95; profiles/maxmono_waves_ab.json).  From 4096 points on the two rings leave LDS for two
+  // waves anyway.  The figures hold with this file's -fno-slp-vectorize (build.py): without it the two largest sizes spill.
+  static constexpr int kWaves = 2;
+};
+
+template <int LOGH>
+__global__ __launch_bounds__(FftGeom<LOGH>::Threads, MaxMonoGeom<LOGH>::kWaves) void k_maxmono_stft(
+    const float* __restrict__ xL, const float* __restrict__ xR, int64_t n, int64_t x_stride, int hop, int s, int rounds, int ring,
+    const float* __restrict__ window, const float2* __restrict__ tw, const float2* __restrict__ post, float* __restrict__ y_max,
+    int64_t ymax_stride, float* __restrict__ y_min, int64_t ymin_stride, int64_t n_frames_i, float fscale, float iscale) {
+  using G = FftGeom<LOGH>;
+  constexpr int H = G::H, T = G::T, n_fft = 2 * H, P = (H / 2) / T;
+  extern __shared__ __attribute__((aligned(16))) float2 lds[];
+  float* acc_max = reinterpret_cast<float*>(lds + G::Frames * G::FrameLds);
+  float* acc_min = acc_max + ring;
+  float* env_tab = acc_min + ring;
+  const int tid = threadIdx.x;
+  const int u = tid / T, j = tid - u * T;
+  float2* X = lds + u * G::FrameLds;
+  const int64_t N = n + H;                           // fix_length(x, n + n_fft // 2)
+  const int NF = G::Frames * rounds, OUT = NF - (s - 1);
+  const int64_t TT_lo = (int64_t)blockIdx.x * OUT * hop, TT_hi = TT_lo + (int64_t)OUT * hop;   // owned overlap-add range
+  const int64_t st_lo = TT_lo > H ? TT_lo : H, st_hi = TT_hi < N ? TT_hi : N;            // ... that is output: t = TT - H < n
+  const int64_t f_start = (int64_t)blockIdx.x * OUT - (s - 1);
+  const int64_t ola_len = (int64_t)n_fft + (int64_t)hop * (n_frames_i - 1);
+  for (int i = tid; i < 2 * ring; i += G::Threads) acc_max[i] = 0.0f;
+  // window-sum-square by phase where every covering frame exists (frames ascending = offsets descending, as K_istft)
+  for (int ph = tid; ph < hop; ph += G::Threads) {
+    float e = 0.0f;
+    for (int o = ph + ((n_fft - 1 - ph) / hop) * hop; o >= 0; o -= hop) e += window[o] * window[o];
+    env_tab[ph] = e;
+  }
+  // per-lane constants of every frame: window taps of the lane's points, untangle twiddles
+  float2 wq[8], pk[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    wq[q] = *reinterpret_cast<const float2*>(window + 2 * (j + q * T));
+    pk[q] = cconj(post[j + q * T]);
+  }
+  float2 pw[P + 1];
+#pragma unroll
+  for (int i = 0; i < P; ++i) pw[i] = post[j + i * T];
+  pw[P] = post[H / 2];
+  const float hs = 0.5f * fscale;
+  // inverse input z[k] = conj(0.5 (ev + i od)) of the selected bins a = X[k], b = X[H - k] (K_istft's operations)
+  auto inv = [&](float2 a, float2 b, float2 cp, bool dc) {
+    if (dc) {
+      a.y = 0.0f;
+      b.y = 0.0f;
+    }
+    b = cconj(b);
+    const float2 ev = cadd(a, b);
+    const float2 od = cmul(cp, csub(a, b));
+    return make_float2(0.5f * (ev.x - od.y), -0.5f * (ev.y + od.x));
+  };
+  __syncthreads();
+  const int64_t interior_lo = n_fft - 1, interior_hi = (int64_t)hop * (n_frames_i - 1);
+  int ring_base = 0;                                                  // slot of position f0 * hop
+  for (int r = 0; r < rounds; ++r) {
+    const int64_t f0 = f_start + (int64_t)r * G::Frames;
+    if (f0 * hop >= st_hi) break;                                   // workgroup-uniform: nothing left to store
+    const int64_t fr = f0 + u;
+    const bool live = fr >= 0 && fr < n_frames_i;
+    const long long base = (long long)fr * hop - H;
+    // gather + window + pack (K_stft's products: window * sample) and the forward transform of one channel
+    auto forward = [&](const float* __restrict__ x) {
+      float2 v[8];
+      if (live && base >= 0 && base + n_fft <= n) {
+        const float* xs = x + base * x_stride;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int t0 = 2 * (j + q * T);
+          v[q] = make_float2(wq[q].x * xs[(int64_t)t0 * x_stride], wq[q].y * xs[(int64_t)(t0 + 1) * x_stride]);
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int t0 = 2 * (j + q * T);
+          float2 z = make_float2(0.0f, 0.0f);
+          if (live) {
+            const long long i0 = reflect_index(base + t0, N), i1 = reflect_index(base + t0 + 1, N);
+            z.x = wq[q].x * (i0 < n ? x[i0 * x_stride] : 0.0f);
+            z.y = wq[q].y * (i1 < n ? x[i1 * x_stride] : 0.0f);
+          }
+          v[q] = z;
+        }
+      }
+      fft_core<LOGH>(v, X, j, tw);
+    };
+    // untangle (K_stft mode 0: X[k] = (ev - i t) / 2 / sqrt(n_fft)) of the pair i: bins k and H - k
+    auto untangle = [&](int i, int sk, int sm, float2& bk, float2& bm) {
+      const float2 zk = X[sk];
+      const float2 zc = cconj(X[sm]);
+      const float2 ev = cadd(zk, zc);
+      const float2 t = cmul(pw[i], csub(zk, zc));
+      bk = make_float2((ev.x + t.y) * hs, (ev.y - t.x) * hs);
+      bm = make_float2((ev.x - t.y) * hs, (-ev.y - t.x) * hs);
+    };
+    forward(xL);
+    float2 lk[P + 1], lm[P + 1];
+#pragma unroll
+    for (int i = 0; i <= P; ++i) {
+      const int k = (i < P) ? j + i * T : H / 2;
+      if (i == P && j != 0) break;
+      untangle(i, lpad(k), lpad((H - k) & (H - 1)), lk[i], lm[i]);
+    }
+    forward(xR);                                                     // its first exchange waits for the reads above
+    // select, and the inverse inputs of the same pair: the max spectrum's written back to the two slots this lane just read
+    // (the pair sets of the lanes are disjoint), the min spectrum's kept for the second inverse
+    float2 zk_min[P + 1], zm_min[P + 1];
+#pragma unroll
+    for (int i = 0; i <= P; ++i) {
+      const int k = (i < P) ? j + i * T : H / 2;
+      if (i == P && j != 0) break;
+      const int sk = lpad(k), sm = lpad((H - k) & (H - 1));
+      float2 rk, rm, xk, nk, xm, nm;
+      untangle(i, sk, sm, rk, rm);
+      select_bin(lk[i], rk, xk, nk);
+      if (i == P) {                                                  // k = H/2 pairs with itself
+        const float2 cp = cconj(post[H / 2]);
+        if (y_max) X[sk] = inv(xk, xk, cp, false);
+        if (y_min) zk_min[i] = inv(nk, nk, cp, false);
+      } else {
+        select_bin(lm[i], rm, xm, nm);                               // bin H - k
+        const float2 cpm = cconj(post[H - k]);
+        if (y_max) {
+          X[sk] = inv(xk, xm, pk[i], k == 0);
+          if (k != 0) X[sm] = inv(xm, xk, cpm, false);
+        }
+        if (y_min) {
+          zk_min[i] = inv(nk, nm, pk[i], k == 0);
+          if (k != 0) zm_min[i] = inv(nm, nk, cpm, false);
+        }
+      }
+    }
+    // inverse transform of the frame buffer's inverse input, windowed, overlap-added into `acc`, frames ascending
+    auto inverse_ola = [&](float* __restrict__ acc) {
+      frame_sync<T>();
+      float2 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = X[lpad(j + q * T)];
+      fft_core<LOGH>(v, X, j, tw);
+      // windowed time samples, in place: y[2i] = re, y[2i+1] = -im of conj(FFT(conj Z)) (K_istft's scaling)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int i = j + q * T;
+        const float2 z = X[lpad(i)];
+        X[lpad(i)] = make_float2(z.x * iscale * wq[q].x, -z.y * iscale * wq[q].y);
+      }
+      __syncthreads();
+      const int span = (G::Frames - 1) * hop + n_fft;
+      for (int p = tid; p < span; p += G::Threads) {
+        int u_hi = p / hop;
+        if (u_hi > G::Frames - 1) u_hi = G::Frames - 1;
+        const int u_lo = p - n_fft + 1 <= 0 ? 0 : (p - n_fft + hop) / hop;
+        int sl = ring_base + p;                                      // p < span <= ring
+        if (sl >= ring) sl -= ring;
+        float a = acc[sl];
+        for (int w = u_lo; w <= u_hi; ++w) {
+          const int64_t fw = f0 + w;
+          if (fw < 0 || fw >= n_frames_i) continue;
+          const int off = p - w * hop;
+          const float2 pr = lds[w * G::FrameLds + lpad(off >> 1)];
+          a += (off & 1) ? pr.y : pr.x;
+        }
+        acc[sl] = a;
+      }
+      __syncthreads();
+    };
+    if (y_max) inverse_ola(acc_max);
+    if (y_min) {                                                     // a NULL output costs neither its inverse input nor its inverse
+#pragma unroll
+      for (int i = 0; i <= P; ++i) {
+        const int k = (i < P) ? j + i * T : H / 2;
+        if (i == P && j != 0) break;
+        X[lpad(k)] = zk_min[i];
+        if (i < P && k != 0) X[lpad(H - k)] = zm_min[i];
+      }
+      inverse_ola(acc_min);
+    }
+    // the round completes [f0 hop, (f0 + Frames) hop): normalise and store what this run owns, clear the ring slots
+    for (int p = tid; p < G::Frames * hop; p += G::Threads) {
+      const int64_t TT = f0 * hop + p;
+      int sl = ring_base + p;
+      if (sl >= ring) sl -= ring;
+      float a = acc_max[sl], b = acc_min[sl];
+      acc_max[sl] = 0.0f;
+      acc_min[sl] = 0.0f;
+      if (TT < TT_lo || TT < st_lo || TT >= st_hi) continue;
+      if (TT < ola_len) {
+        float env;
+        if (TT >= interior_lo && TT <= interior_hi) {
+          env = env_tab[TT % hop];
+        } else {
+          int64_t e_hi = TT / hop;
+          if (e_hi > n_frames_i - 1) e_hi = n_frames_i - 1;
+          const int64_t e_lo = (TT - n_fft + 1 <= 0) ? 0 : (TT - n_fft + hop) / hop;
+          env = 0.0f;
+          for (int64_t e = e_lo; e <= e_hi; ++e) {
+            const float w = window[TT - e * hop];
+            env += w * w;
+          }
+        }
+        if (env > 1.17549435e-38f) {                                  // > tiny(float32)  (util/fourier.py:414-415)
+          a /= env;
+          b /= env;
+        }
+      } else {
+        a = 0.0f;
+        b = 0.0f;
+      }
+      if (y_max) y_max[(TT - H) * ymax_stride] = a;
+      if (y_min) y_min[(TT - H) * ymin_stride] = b;
+    }
+    ring_base += G::Frames * hop;                                    // Frames * hop < ring
+    if (ring_base >= ring) ring_base -= ring;
+  }
+}
+
 }  // namespace par
 
 extern "C" {
@@ -2835,5 +3092,105 @@ extern "C" int par_gate_stft_f32(int device, const float* x, int64_t n, int64_t 
     return launch_with_lds(k_gate_stft<decltype(lh)::value>, dim3((unsigned)runs, (unsigned)n_ch), dim3(FftGeom<decltype(lh)::value>::Threads),
                            lds, device, as_stream(stream), x, n, x_stride, hop, s, rounds, ring, window, tw.w, tw.post, cutoff, low, y,
                            y_stride, nfi, fscale, iscale);
+  });
+}
+
+// ---- MaxMono entry points (added at ABI 109) -----------------------------------------------------------------------------------
+static bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return a && b && pa < pb + bytes && pb < pa + bytes;
+}
+
+extern "C" int par_select_spectrum_f32(int device, const float* specL, const float* specR, int64_t n_frames, int64_t bins, int64_t pitch,
+                                       float* out_max, float* out_min, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(specL && specR && (out_max || out_min), PAR_ERR_ARG, "par_select_spectrum_f32: null pointer");
+  const int64_t p = pitch ? pitch : bins;
+  PAR_REQUIRE(n_frames >= 0 && bins >= 1 && p >= bins, PAR_ERR_ARG, "par_select_spectrum_f32: bad sizes (frames %lld, bins %lld, pitch %lld)",
+              (long long)n_frames, (long long)bins, (long long)pitch);
+  PAR_REQUIRE(ceil_div(bins, 256) <= 0x7fffffff, PAR_ERR_UNSUPPORTED, "par_select_spectrum_f32: too many bins");
+  if (n_frames == 0) return PAR_OK;
+  const size_t bytes = (size_t)((n_frames - 1) * p + bins) * sizeof(float2);
+  PAR_REQUIRE(!ranges_overlap(out_max, specL, bytes) && !ranges_overlap(out_max, specR, bytes) && !ranges_overlap(out_min, specL, bytes) &&
+                  !ranges_overlap(out_min, specR, bytes) && !ranges_overlap(out_max, out_min, bytes),
+              PAR_ERR_ARG, "par_select_spectrum_f32: an output overlaps an input or the other output");
+  PAR_HIP_CHECK(hipSetDevice(device));
+  const int64_t gy = n_frames < 4096 ? n_frames : 4096;
+  hipLaunchKernelGGL(k_select_spectrum, dim3((unsigned)ceil_div(bins, 256), (unsigned)gy), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const float2*>(specL), reinterpret_cast<const float2*>(specR), n_frames, bins, p,
+                     reinterpret_cast<float2*>(out_max), reinterpret_cast<float2*>(out_min));
+  PAR_HIP_CHECK(hipGetLastError());
+  return PAR_OK;
+}
+
+static int maxmono_stft_sizes(int64_t n, int n_fft, int hop, int64_t* n_frames_i, int* s, int* rounds, int* ring, int64_t* runs,
+                              size_t* lds, int* frames_per_round) {
+  using namespace par;
+  if (n < 1 || hop < 1 || hop > n_fft || n_fft < 16 || n_fft > 8192 || (n_fft & (n_fft - 1))) return PAR_ERR_UNSUPPORTED;
+  const int64_t frames = par_stft_frames(n + n_fft / 2, n_fft, hop);                    // STFT of fix_length(x, n + n_fft/2)
+  const int64_t want = ceil_div(n + n_fft, hop);                                        // istft(length=n) keeps these
+  *n_frames_i = frames < want ? frames : want;
+  *s = (int)ceil_div(n_fft, hop);
+  return dispatch_logh<3, 12>(ilog2(n_fft / 2), [&](auto lh) {
+    using MG = MaxMonoGeom<decltype(lh)::value>;
+    *frames_per_round = MG::G::Frames;
+    *rounds = MG::rounds(*s);
+    *ring = MG::ring(hop);
+    *lds = MG::lds(hop);
+    *runs = ceil_div(n + n_fft / 2, (int64_t)(MG::G::Frames * *rounds - (*s - 1)) * hop);
+    return (*lds <= 160 * 1024) ? PAR_OK : PAR_ERR_UNSUPPORTED;
+  });
+}
+
+extern "C" int par_maxmono_stft_supported(int n_fft, int hop) {
+  int64_t nfi = 0, runs = 0;
+  int s = 0, rounds = 0, ring = 0, frames_per_round = 0;
+  size_t lds = 0;
+  return maxmono_stft_sizes(1, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds, &frames_per_round) == PAR_OK;
+}
+
+extern "C" int64_t par_maxmono_stft_transformed_frames(int64_t n, int n_fft, int hop) {
+  int64_t nfi = 0, runs = 0;
+  int s = 0, rounds = 0, ring = 0, frames_per_round = 0;
+  size_t lds = 0;
+  if (maxmono_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds, &frames_per_round) != PAR_OK) return 0;
+  // every run but the last transforms all its rounds; the last stops once its rounds reach the end of the output
+  const int64_t out = (int64_t)frames_per_round * rounds - (s - 1);
+  int64_t total = 0;
+  for (int64_t b = 0; b < runs; ++b) {
+    const int64_t f_start = b * out - (s - 1), st_hi = (b + 1) * out * hop < n + n_fft / 2 ? (b + 1) * out * hop : n + n_fft / 2;
+    for (int r = 0; r < rounds; ++r) {
+      if ((f_start + (int64_t)r * frames_per_round) * hop >= st_hi) break;
+      total += frames_per_round;
+    }
+  }
+  return total;
+}
+
+extern "C" int par_maxmono_stft_f32(int device, const float* xL, const float* xR, int64_t n, int64_t x_stride, int n_fft, int hop,
+                                    const float* window, float* y_max, int64_t ymax_stride, float* y_min, int64_t ymin_stride,
+                                    void* stream) {
+  using namespace par;
+  PAR_REQUIRE(xL && xR && window && (y_max || y_min), PAR_ERR_ARG, "par_maxmono_stft_f32: null pointer");
+  PAR_REQUIRE(n >= 1 && x_stride >= 1 && (!y_max || ymax_stride >= 1) && (!y_min || ymin_stride >= 1) && hop >= 1, PAR_ERR_ARG,
+              "par_maxmono_stft_f32: bad sizes (n %lld, strides %lld / %lld / %lld, hop %d)", (long long)n, (long long)x_stride,
+              (long long)ymax_stride, (long long)ymin_stride, hop);
+  int64_t nfi = 0, runs = 0;
+  int s = 0, rounds = 0, ring = 0, frames_per_round = 0;
+  size_t lds = 0;
+  PAR_REQUIRE(maxmono_stft_sizes(n, n_fft, hop, &nfi, &s, &rounds, &ring, &runs, &lds, &frames_per_round) == PAR_OK, PAR_ERR_UNSUPPORTED,
+              "par_maxmono_stft_f32: n_fft=%d hop=%d (a power of two in [16, 8192], 1 <= hop <= n_fft, two rings within 160 KB of LDS)",
+              n_fft, hop);
+  PAR_REQUIRE(runs <= 0x7fffffff, PAR_ERR_UNSUPPORTED, "par_maxmono_stft_f32: signal too long");
+  PAR_HIP_CHECK(hipSetDevice(device));
+  Twiddles tw;
+  int rc = get_twiddles(device, n_fft, &tw);
+  if (rc != PAR_OK) return rc;
+  const float fscale = (float)(1.0 / sqrt((double)n_fft));
+  const float iscale = (float)(sqrt((double)n_fft) / (double)(n_fft / 2));
+  return dispatch_logh<3, 12>(ilog2(n_fft / 2), [&](auto lh) {
+    return launch_with_lds(k_maxmono_stft<decltype(lh)::value>, dim3((unsigned)runs), dim3(FftGeom<decltype(lh)::value>::Threads), lds,
+                           device, as_stream(stream), xL, xR, n, x_stride, hop, s, rounds, ring, window, tw.w, tw.post, y_max,
+                           ymax_stride, y_min, ymin_stride, nfi, fscale, iscale);
   });
 }
