@@ -562,11 +562,15 @@ int par_mean_mag_frames_f32(int device, const float* mag, int64_t n_frames, int6
  *          (window offsets -(k/2) .. k-1-k/2, the element of rank k/2, half-sample symmetric reflection repeated as often as
  *          the axis needs; 1 <= k <= PAR_HPSS_MAX_KERNEL, odd or even).  |S| is numpy's complex64 np.abs (see
  *          par_gate_spectrum_f32, without its + 1e-7): the medians are selections and equal scipy's on np.abs(spec) bit for bit.
+ *          A NaN magnitude ranks above inf in a window (np.sort's order): a median is NaN when the element of rank k/2 is.
  *   mask_h = softmask(harm, perc * margin_h), mask_p = softmask(perc, harm * margin_p) in float32: Z = max(X, Xref);
  *          Z < FLT_MIN -> 0.5 when both margins are 1, else 0; else (X/Z)^power / ((X/Z)^power + (Xref/Z)^power) (power 2
- *          squares, 1 and 0.5 are exact too); power = +inf: the hard mask X > Xref.
+ *          squares, 1 and 0.5 are exact too); power = +inf: the hard mask X > Xref.  The masks propagate NaN as numpy does
+ *          (np.maximum keeps it): a NaN in X or Xref gives a NaN mask for every finite power, and 0 from the hard mask.
  * out_kind PAR_HPSS_COMPONENTS: out_h = S * mask_h, out_p = S * mask_p (the input's type);  PAR_HPSS_MASKS: the two float32 masks;
  * PAR_HPSS_HARMONIC: out_h = S * mask_h only (out_p may be NULL; decompose.harmonic);  PAR_HPSS_MEDIANS: float32 harm and perc.
+ * S * mask is numpy's product: for complex64 the complex product with mask + 0i, so an infinite or NaN part of S makes both
+ * parts of the result NaN and a zero result has numpy's sign; finite non-zero parts are scaled one by one.
  * Outputs are DEVICE [n_frames][pitch] arrays of their element type and must not overlap spec or each other.  No scratch.
  * Kernel sizes outside 1..99, power <= 0 (or NaN), a margin below 1 and null pointers: PAR_ERR_ARG before any device call. */
 #define PAR_HPSS_MAX_KERNEL 99

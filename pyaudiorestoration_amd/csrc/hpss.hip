@@ -16,7 +16,8 @@
 // whatever k is (1..99), no per-k code and no register array of k elements.  A lane selects kRun consecutive outputs of its column
 // at once: their windows overlap in all but kRun - 1 elements, so one LDS read feeds kRun compare-and-count pairs.
 //
-// Built with -ffp-contract=off: the mask's a*a + b*b and S x mask round every step separately, as numpy does.
+// Built with -ffp-contract=off: the mask's a*a + b*b and S x mask round every step separately, as numpy does (the one fused
+// product of numpy's complex64 x float32 is spelled as an fmaf: np_mul_c64_f32).
 #include "par_common.h"
 #include "np_abs.h"
 #include <math.h>
@@ -100,9 +101,12 @@ __device__ __forceinline__ void select_run(const uint32_t* __restrict__ col, int
 }
 
 // decompose.softmask in float32: Z = max(X, Xref); Z < FLT_MIN (subnormals included, whatever the denormal mode: the bit
-// patterns are compared) -> bad_value; else (X/Z)^p / ((X/Z)^p + (Xref/Z)^p); the hard mask is X > Xref
+// patterns are compared) -> bad_value; else (X/Z)^p / ((X/Z)^p + (Xref/Z)^p); the hard mask is X > Xref (false on a NaN).
+// np.maximum keeps a NaN where fmaxf drops it: a NaN in X or Xref makes Z, both ratios and the mask NaN, also beside an
+// Xref or X under FLT_MIN, where fmaxf alone would answer bad_value.
 __device__ __forceinline__ float softmask(float x, float xref, int pow_mode, float power, float bad_value) {
   if (pow_mode == kPowHard) return x > xref ? 1.0f : 0.0f;
+  if (x != x || xref != xref) return __builtin_nanf("");
   const float z = fmaxf(x, xref);
   if (__float_as_uint(z) < 0x00800000u) return bad_value;
   float a = x / z, b = xref / z;
@@ -117,6 +121,14 @@ __device__ __forceinline__ float softmask(float x, float xref, int pow_mode, flo
     b = powf(b, power);
   }
   return a / (a + b);
+}
+
+// numpy's complex64 * float32: the mask is promoted to m + 0i and the full complex product is formed, in numpy's vector loop as
+// re = fma(s.re, m, -(s.im * 0)), im = fma(s.re, 0, s.im * m) = s.re * 0 + s.im * m.  For finite non-zero parts that is
+// (s.re * m, s.im * m); the products with the 0 make both parts NaN when either part of S is infinite or NaN and decide the sign
+// of a zero result, and the one fused product keeps the sign of a real part that underflows.
+__device__ __forceinline__ float2 np_mul_c64_f32(float2 s, float m) {
+  return make_float2(fmaf(s.x, m, -(s.y * 0.0f)), s.x * 0.0f + s.y * m);
 }
 
 template <bool kComplex>
@@ -180,8 +192,8 @@ __global__ __launch_bounds__(kHpssThreads) void k_hpss(const void* __restrict__ 
         static_cast<float*>(out_p)[idx] = mp;
       } else if (kComplex) {
         const float2 s = static_cast<const float2*>(spec)[idx];
-        static_cast<float2*>(out_h)[idx] = make_float2(s.x * mh, s.y * mh);
-        if (p.out_kind == kOutComponents) static_cast<float2*>(out_p)[idx] = make_float2(s.x * mp, s.y * mp);
+        static_cast<float2*>(out_h)[idx] = np_mul_c64_f32(s, mh);
+        if (p.out_kind == kOutComponents) static_cast<float2*>(out_p)[idx] = np_mul_c64_f32(s, mp);
       } else {
         const float s = static_cast<const float*>(spec)[idx];
         static_cast<float*>(out_h)[idx] = s * mh;

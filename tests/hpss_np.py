@@ -48,6 +48,34 @@ def mask(x, xref, power, both_margins_one):
     return np.where(small, np.float32(0.5 if both_margins_one else 0.0), m)
 
 
+def mask64(x, xref, power, both_margins_one):
+    """the soft mask with its arithmetic in float64: the ratios x / z and xref / z are the float32 quotients both the kernel and
+    `mask` form, the power, the sum and the quotient are float64, rounded to float32 once.  The exponent is the float32 value of
+    `power`, which is what numpy raises a float32 array to and what the kernel passes to powf (0.3 is float32(0.3) on both sides;
+    with the float64 0.3, 1e-30 ** 0.3 alone moves by 8 float32 ulp).  A NaN in x or xref passes through np.maximum into z and
+    from there into the mask, as in `mask`."""
+    x, xref = np.asarray(x, np.float32), np.asarray(xref, np.float32)
+    if np.isinf(power):
+        return x > xref
+    z = np.maximum(x, xref)
+    small = z < TINY
+    z = np.where(small, np.float32(1), z)
+    with np.errstate(all="ignore"):
+        a, b = x / z, xref / z
+        assert a.dtype == b.dtype == np.float32
+        a, b = a.astype(np.float64) ** float(np.float32(power)), b.astype(np.float64) ** float(np.float32(power))
+        m = (a / (a + b)).astype(np.float32)
+    return np.where(small, np.float32(0.5 if both_margins_one else 0.0), m)
+
+
+def ulp_distance_nan(a, b):
+    """(the NaN patterns are the same, largest float32 ulp distance over the cells that are NaN in neither)"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    na, nb = np.isnan(a), np.isnan(b)
+    ok = ~(na | nb)
+    return bool(np.array_equal(na, nb)), ulp_distance(a[ok], b[ok])
+
+
 def masks(mag, kernel=(31, 31), power=2.0, margin=(1.0, 1.0)):
     harm, perc = medians(mag, *kernel)
     one = margin[0] == 1 and margin[1] == 1
