@@ -603,8 +603,9 @@ int par_resample_fixed_f32(int device, const float* x, int64_t n, int64_t x_stri
                            float* y, int64_t n_out, int64_t y_stride, void* stream);
 /* ---- renoiser "Gauge offset" (renoiser_gui.py:347-369 sniff_offset, experiments/renoiser.py:59-73) -----------------------------
  * par_gauge_frames, par_gauge_scratch_bytes and par_gauge_offset_f32 are added at ABI 109: par_version() stays 109. */
-/* Frames of the reference's STFT for pad `offset`: (n + offset + n_fft/2) / hop + 1 (host only; -1 for n < 0, n_fft < 2,
- * hop < 1 or a negative offset). */
+/* Frames of the reference's STFT for pad `offset`: with M = n + offset + n_fft/2 samples, reflect-padded by n_fft/2 at both
+ * ends, (M + 2 (n_fft/2) - n_fft) / hop + 1 -- for an even n_fft (n + offset + n_fft/2) / hop + 1 (host only; -1 for n < 0,
+ * n_fft < 2, hop < 1 or a negative offset). */
 int64_t par_gauge_frames(int64_t n, int n_fft, int hop, int offset);
 /* Bytes of DEVICE scratch par_gauge_offset_f32 needs (host only; 0 for arguments it refuses): three float64 sums per dense
  * workgroup and residue slot, and one complex64 per pad and edge frame. */

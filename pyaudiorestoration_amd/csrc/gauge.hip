@@ -5,8 +5,8 @@
 // vector h (renoiser.gauge_filter), so every (pad, frame) value is one tap sum
 //     z(i, j) = sum_m p_i[j hop + m] h[m],      m = 0 .. n_fft - 1 ascending, float32, one FMA per tap and part,
 // over the padded signal p_i.  With half = n_fft / 2 and M = n + i + half, padded index q maps to r = q - half; r < 0 reflects
-// to -r, r >= M to 2 (M - 1) - r; the value is x[r - i] for i <= r < i + n and 0 elsewhere (an r the reflection leaves outside
-// [0, M) -- odd n_fft only -- reads 0).
+// to -r, r >= M to 2 (M - 1) - r; the value is x[r - i] for i <= r < i + n and 0 elsewhere.  The padded signal has M + 2 half
+// samples and so (M + 2 half - n_fft) / hop + 1 frames (ga_frames): no frame reads past it, also for an odd n_fft.
 //
 // A frame whose window touches no reflected sample starts at signal position t = j hop - half - i and reads the zero-extended
 // signal xe[t .. t + n_fft): for 0 <= t <= n + half - n_fft every t belongs to exactly one (i, j), i = (-(t + half)) mod hop.
@@ -43,6 +43,7 @@ static_assert(kGaLds >= 2 * kGaTile, "the tile's z (float2) reuse the staging bu
 struct GaGeom {
   int64_t n, xs;
   int n_fft, hop, half;
+  int ext;                // half - (n_fft odd): the last frame starts at or before n + i + ext (ga_frames)
   int64_t dense;          // dense positions t = 0 .. dense - 1 (0: none)
   int64_t n_wg;           // dense workgroups
   int slots;              // residue slots per workgroup: min(hop, kGaTile)
@@ -50,7 +51,10 @@ struct GaGeom {
   int edge_blocks;        // workgroups that take the edges hop edge lanes
 };
 
-__host__ __device__ inline int64_t ga_frames(int64_t n, int half, int hop, int i) { return (n + i + half) / hop + 1; }
+// frames of the signal of M = n + i + half samples reflect-padded by half at both ends: (M + 2 half - n_fft) / hop + 1, which is
+// (n + i + half) / hop + 1 for an even n_fft and one frame fewer where hop divides M for an odd one.  ext = 3 half - n_fft (GaGeom)
+__host__ __device__ inline int ga_ext(int n_fft) { return n_fft / 2 - (n_fft & 1); }
+__host__ __device__ inline int64_t ga_frames(int64_t n, int ext, int hop, int i) { return (n + i + ext) / hop + 1; }
 // dense frames of pad i: j_lo .. j_hi (inclusive; empty when j_lo > j_hi)
 __host__ __device__ inline int64_t ga_j_lo(const GaGeom& g, int i) { return ((int64_t)g.half + i + g.hop - 1) / g.hop; }
 __host__ __device__ inline int64_t ga_j_hi(const GaGeom& g, int i) {
@@ -144,7 +148,7 @@ __device__ __forceinline__ void ga_dense(const float* __restrict__ x, const floa
 
 // edge frame e of pad i -> frame number (a frame past the last one: -1)
 __device__ __forceinline__ int64_t ga_edge_frame(const GaGeom& g, int i, int e) {
-  const int64_t j_lo = ga_j_lo(g, i), j_hi = ga_j_hi(g, i), frames = ga_frames(g.n, g.half, g.hop, i);
+  const int64_t j_lo = ga_j_lo(g, i), j_hi = ga_j_hi(g, i), frames = ga_frames(g.n, g.ext, g.hop, i);
   int64_t j;
   if (j_lo > j_hi) j = e;                             // no dense frame: every frame is an edge frame
   else j = e < j_lo ? e : j_hi + 1 + (e - j_lo);
@@ -229,7 +233,7 @@ __global__ __launch_bounds__(kGaBlock) void k_gauge_final(const double* __restri
     __syncthreads();
   }
   if (th == 0) {
-    const double F = (double)ga_frames(g.n, g.half, g.hop, i);
+    const double F = (double)ga_frames(g.n, g.ext, g.hop, i);
     const double mr = red[0][0] / F, mi = red[1][0] / F;
     const double var = red[2][0] / F - (mr * mr + mi * mi);
     stds[i] = sqrt(var > 0.0 ? var : var == var ? 0.0 : var);      // the clamp keeps a NaN
@@ -239,13 +243,13 @@ __global__ __launch_bounds__(kGaBlock) void k_gauge_final(const double* __restri
 // false: the sizes do not fit the index arithmetic
 static bool ga_geometry(int64_t n, int64_t xs, int n_fft, int hop, GaGeom* g) {
   if (n > (int64_t)1 << 46) return false;
-  g->n = n, g->xs = xs, g->n_fft = n_fft, g->hop = hop, g->half = n_fft / 2;
+  g->n = n, g->xs = xs, g->n_fft = n_fft, g->hop = hop, g->half = n_fft / 2, g->ext = ga_ext(n_fft);
   const int64_t dense = n + g->half - n_fft + 1;
   g->dense = dense > 0 ? dense : 0;
   g->n_wg = ceil_div(g->dense, kGaTile);
   g->slots = hop < kGaTile ? hop : kGaTile;
-  // per pad: frames before the first dense one, j hop < half + i, and after the last, up to (n + i + half) / hop -- or, with
-  // no dense frame at all, every frame
+  // per pad: frames before the first dense one, j hop < half + i, and after the last, up to (n + i + ext) / hop --
+  // or, with no dense frame at all, every frame (tests/gauge_inputs.py replays this count against ga_frames)
   int64_t edges;
   if (g->dense > 0) edges = ((int64_t)g->half + hop - 1) / hop + 1 + ((int64_t)n_fft - g->half) / hop + 2;
   else edges = (n + hop - 1 + g->half) / hop + 1;
@@ -263,7 +267,7 @@ static size_t ga_partial_bytes(const GaGeom& g) { return (size_t)g.n_wg * g.slot
 
 extern "C" int64_t par_gauge_frames(int64_t n, int n_fft, int hop, int offset) {
   if (n < 0 || n_fft < 2 || hop < 1 || offset < 0) return -1;
-  return par::ga_frames(n, n_fft / 2, hop, offset);
+  return par::ga_frames(n, par::ga_ext(n_fft), hop, offset);
 }
 
 extern "C" size_t par_gauge_scratch_bytes(int64_t n, int n_fft, int hop) {
