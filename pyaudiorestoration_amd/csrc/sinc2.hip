@@ -10,13 +10,16 @@
 // to 8; outputs whose centre lies beyond it (a handful: periods differ from 1 by <= 1.25 %) simply open the next pass.
 //   * taps 3 <= |n| <= 31 at fc = 1: a Farrow bank in q = shift^2 (minimax polynomials of (win_n/pi)/(n^2 - q),
 //     tools/sinc2_model.py) -- six fixed FIR filters on the input grid, evaluated for the pass's 128 centres on the matrix cores
-//     (v_mfma_f32_16x16x32_f16, signal and dominant filter pair split float16 hi + lo 2^-12: 13 MFMAs since r06); the bank goes through
-//     the wave's own LDS and every output gathers its centre's row;
+//     (v_mfma_f32_16x16x32_f16, signal and dominant filter pair split float16 hi + lo 2^-12: 13 MFMAs since r06, 11 since r11 --
+//     the third K slice, 8 % full, folded into one product: see bank_load); the bank goes through the wave's own LDS and every
+//     output gathers its centre's row;
 //   * fc < 1 (read head slower than the output clock) = the fc = 1 result + a correction in g = 1 - fc whose taps are ENTIRE
 //     functions of g (n - s): all 63 taps enter through seven fixed MOMENT filters m_i = sum_n (-1)^n win_n (n/32)^i x[c + n]
-//     on the same image (18 more MFMAs; 15 to order 5 where every lane of the pass has g <= 0.0105, r06) and a complex Horner in 32 pi g per output (tools/sinc3_model.py; 1e-7 of the peak for
+//     on the same image (18 more MFMAs to order 6, with the bank's 13 unfolded: 31; 13 more to order 5 where every lane of the pass
+//     has g <= 0.0105, the (m0 m1) pair's third slice folded like the bank's: 24, r11) and a complex Horner in 32 pi g per output (tools/sinc3_model.py; 1e-7 of the peak for
 //     g <= 0.0101, 5e-7 to 0.0125; steeper tiles go to the block kernel).  One image, per-lane g exact, no restarts;
-//   * the 25 constant fragments of both filter sets RESIDENT IN REGISTERS for the life of the wave (the fc = 1 kernel <1, 1>: its 10);
+//   * the constant fragments of both filter sets RESIDENT IN REGISTERS for the life of the wave: 21 + the two folded ones (the fc = 1
+//     kernel <1, 1>: 8 + 1); a pass of the order-6 loop swaps the folded ones for the four slice-2 fragments it still multiplies by;
 //   * taps |n| <= 2 on the vector units with the lane's exact shift (two reciprocals per output);
 //   * the input streams through a ring per wave (8 chunks of 128 float32 samples, direct-to-LDS loads two passes ahead),
 //     converted ONCE to float16 hi / lo images for the banks -- no halo is ever re-read or re-converted; block records of the
@@ -242,7 +245,7 @@ __device__ __forceinline__ S2Row s2_place_row(const uint4 ra, const uint4 rb, co
 //              minimum pinned to a scalar register (r10) -- rides beside it.  Seven passes in eight lie inside one tile and
 //              take both rows' anchor from one add; the pass that straddles a tile border selects per lane in a block of
 //              its own, behind a scalar branch and out of the loop's line
-//     READS    BANK(k + 1)'s six image fragments, as soon as ws is known
+//     READS    BANK(k + 1)'s image fragments (fc = 1: five, xv among them; fc < 1: six), as soon as ws is known
 //     OUT(k)   arithmetic, pinned here: the fragments land under it -- both rows in the fc = 1 and the order-6 loop; in the
 //              order-5 loop (the benchmark's fc < 1 passes) the first row only
 //     BANK(k + 1) MFMAs -- order 5: OUT(k)'s second row dealt out behind them, two vector instructions to an MFMA (which hides
@@ -300,37 +303,73 @@ struct S3Pass {                                  // a placed pass: 128 candidate
 };
 
 // fc = 1 bank AND the seven moment filters of the fc < 1 correction over the same 128 centres, from the same signal fragments:
-// 15 + 18 MFMAs.  fr: the fc = 1 bank's ten constant fragments (kBank2Frags32's first ten), fmr: the moment filters' fifteen
-// (kBank3Frags32, sinc_taps_gen.h); all resident in the wave's registers.  MOMENTS = false: the fc = 1 bank alone.
+// 13 + 18 MFMAs to order 6, 11 + 13 to order 5, 11 for the bank alone.  fr: the fc = 1 bank's ten constant fragments (kBank2Frags32's
+// first ten), fmr: the moment filters' fifteen (kBank3Frags32, sinc_taps_gen.h), both without the dominant pairs' slice 2, which
+// is fsw's (below); resident in the wave's registers.  MOMENTS = false: the fc = 1 bank alone.
 constexpr int kCtabUnity = 10;
 // SIX = false: without the moment of order 6 (passes with 1 - fc <= 0.0105: the series to order 5 is within 1.6e-6 there)
-// (in two halves: the six signal fragments read from the images, and the matrix work with the row writes)
+// (in two halves: the signal fragments read from the images -- five, six with the moment filters -- and the matrix work with the row writes)
 struct S3Frags {
   half8v xh[3], xl[3];
+  half8v xv;                                     // the folded slice 2's mixed fragment (below)
 };
-template <class LDS>
-__device__ __forceinline__ S3Frags bank_load(const LDS& L, const int offs, const int l, const int ch = 0) {
+// The third K slice folded (r11).  Slice 2 of a filter pair holds only the overhang -- taps 33 - i .. 31 of sub-position i >= 2: K
+// entries 64 .. 69, lanes g = 0 of its fragments, 42 of 512 elements; lanes 16-63 are zero (tools/sinc2_model.py asserts it) --
+// and a K index only has to mean the same thing in A and B.  So the dominant pair's three slice-2 products (hi hi; lo hi and
+// hi lo) are ONE MFMA into the lo accumulator: the constant fragment V (kBank2FoldFrag32 / kBank3FoldFrag32) carries under K
+// group g = 0 the pair's hi slice 2 x 4096 (exact in float16; the accumulator's 2^-12 brings it back), g = 1 its lo slice 2,
+// g = 2 its hi slice 2, g = 3 zeros; the signal fragment xv has image samples 64 .. 71 of the lane's block under every group --
+// the lo image's in the lanes g = 2, the hi image's elsewhere (xv_img: the lane's block and image as byte offsets, formed once
+// per run of a loop; the images are a power of two long, so the image is OR-ed behind the ring's mask: two vector instructions
+// for the address).
+// FOLD passes read neither xl[2] nor, without the moment filters, xh[2].  The order-6 loop keeps its three full slices.
+struct S3XvLane {
+  unsigned at, img;                              // bytes: the lane's block + K entry 64 in an image; the lane's image
+};
+__device__ __forceinline__ S3XvLane bank_xv_img(const int l) {
+  return S3XvLane{16u * (unsigned)(l & 15) + 64u * (unsigned)sizeof(_Float16), (l >> 4) == 2 ? (unsigned)(kRingH * sizeof(_Float16)) : 0u};
+}
+template <bool FOLD, bool XH2, class LDS>
+__device__ __forceinline__ S3Frags bank_load(const LDS& L, const int offs, const int l, const S3XvLane xv_img, const int ch = 0) {
   const int bb = l & 15, g = l >> 4;
-  const int i0 = offs + 8 * bb + 8 * g;
+  // (byte offsets into an image, masked as bytes: as element indices every fragment's address paid a shift behind its mask)
+  constexpr unsigned kImgBytes = kRingH * sizeof(_Float16);
+  const unsigned b0 = (unsigned)offs * (unsigned)sizeof(_Float16) + 16u * (unsigned)(bb + g);
+  const char* const hi = reinterpret_cast<const char*>(&L.img[2 * ch][0]);
+  const char* const lo = reinterpret_cast<const char*>(&L.img[2 * ch + 1][0]);
   S3Frags X;
 #pragma unroll
   for (int ks = 0; ks < 3; ++ks) {
-    const int ix = (i0 + 32 * ks) & (kRingH - 1);
-    X.xh[ks] = *reinterpret_cast<const half8v*>(&L.img[2 * ch][ix]);
-    X.xl[ks] = *reinterpret_cast<const half8v*>(&L.img[2 * ch + 1][ix]);
+    const unsigned at = (b0 + 64u * ks) & (kImgBytes - 1u);
+    X.xh[ks] = X.xl[ks] = half8v{};
+    if (ks < 2 || !FOLD || XH2) X.xh[ks] = *reinterpret_cast<const half8v*>(hi + at);
+    if (ks < 2 || !FOLD) X.xl[ks] = *reinterpret_cast<const half8v*>(lo + at);
+  }
+  X.xv = half8v{};
+  if constexpr (FOLD) {
+    static_assert(sizeof(L.img[0]) == kImgBytes, "the lo image lies kImgBytes behind the hi image");
+    const unsigned at = (((unsigned)offs * (unsigned)sizeof(_Float16) + xv_img.at) & (kImgBytes - 1u)) | xv_img.img;
+    X.xv = *reinterpret_cast<const half8v*>(hi + at);
   }
   return X;
 }
+// fsw: the four constant fragments that depend on the loop -- folded passes: {V2, V3, -, -}; order 6: slice 2 of (e0 d0) hi, lo and
+// of (m0 m1) hi, lo (fragments 2, 7 of the bank, 2, 5 of the moment filters), which fr / fmr do not hold
+constexpr bool bank_folds(bool moments, bool six) { return !(moments && six); }
 template <bool MOMENTS, bool SIX = true, class LDS>
 __device__ __forceinline__ void bank_math(LDS& L, const half8v (&fr)[kBank2Frags], const half8v (&fmr)[kBank3Frags],
-                                          const S3Frags& X, const int l) {
+                                          const half8v (&fsw)[4], const S3Frags& X, const int l) {
+  constexpr bool FOLD = bank_folds(MOMENTS, SIX);
+  constexpr int NS = FOLD ? 2 : 3;               // full slices of the dominant pairs
   const int bb = l & 15, g = l >> 4;
   const half8v (&xh)[3] = X.xh, (&xl)[3] = X.xl;
-  auto frag = [&](int f) { return f < kCtabUnity ? fr[f] : fmr[f - kCtabUnity]; };
+  auto frag = [&](int f) {
+    return f == 2 ? fsw[0] : f == 7 ? fsw[1] : f == kCtabUnity + 2 ? fsw[2] : f == kCtabUnity + 5 ? fsw[3] : f < kCtabUnity ? fr[f] : fmr[f - kCtabUnity];
+  };
   const float4v z = {0.0f, 0.0f, 0.0f, 0.0f};
   float4v e0 = z, lo = z, e1 = z, e2 = z;
 #pragma unroll
-  for (int ks = 0; ks < 3; ++ks) {
+  for (int ks = 0; ks < NS; ++ks) {
     const half8v f0 = frag(ks);
     e0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0, xh[ks], e0, 0, 0, 0);
     lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(5 + ks), xh[ks], lo, 0, 0, 0);
@@ -341,18 +380,22 @@ __device__ __forceinline__ void bank_math(LDS& L, const half8v (&fr)[kBank2Frags
       e2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(8 + ks), xh[ks], e2, 0, 0, 0);
     }
   }
+  if constexpr (FOLD) lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(fsw[0], X.xv, lo, 0, 0, 0);      // slice 2: hi hi x 4096 + lo hi + hi lo
   // (the factor in a vector register: a VALU instruction with an SGPR operand issues at 4.3 cycles instead of 2.4, tools/exp/valu_forms.hip)
   float lo_inv = kBank2LoInv;
   asm volatile("" : "+v"(lo_inv));
   const float4v v0 = e0 + lo * lo_inv, v1 = e1;
   float4v a01 = z, l01 = z, a23 = z, a45 = z, a6 = z;
   if (MOMENTS) {
+    if constexpr (FOLD) l01 = __builtin_amdgcn_mfma_f32_16x16x32_f16(fsw[1], X.xv, l01, 0, 0, 0);
 #pragma unroll
     for (int ks = 0; ks < 3; ++ks) {
-      const half8v f01 = frag(kCtabUnity + ks);
-      a01 = __builtin_amdgcn_mfma_f32_16x16x32_f16(f01, xh[ks], a01, 0, 0, 0);
-      l01 = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(kCtabUnity + 3 + ks), xh[ks], l01, 0, 0, 0);
-      l01 = __builtin_amdgcn_mfma_f32_16x16x32_f16(f01, xl[ks], l01, 0, 0, 0);
+      if (ks < NS) {
+        const half8v f01 = frag(kCtabUnity + ks);
+        a01 = __builtin_amdgcn_mfma_f32_16x16x32_f16(f01, xh[ks], a01, 0, 0, 0);
+        l01 = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(kCtabUnity + 3 + ks), xh[ks], l01, 0, 0, 0);
+        l01 = __builtin_amdgcn_mfma_f32_16x16x32_f16(f01, xl[ks], l01, 0, 0, 0);
+      }
       a23 = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(kCtabUnity + 6 + ks), xh[ks], a23, 0, 0, 0);
       a45 = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(kCtabUnity + 9 + ks), xh[ks], a45, 0, 0, 0);
       if constexpr (SIX) a6 = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(kCtabUnity + 12 + ks), xh[ks], a6, 0, 0, 0);
@@ -377,8 +420,8 @@ __device__ __forceinline__ void bank_math(LDS& L, const half8v (&fr)[kBank2Frags
 }
 template <bool MOMENTS, bool SIX = true, class LDS>
 __device__ __forceinline__ void bank_image3m(LDS& L, const half8v (&fr)[kBank2Frags], const half8v (&fmr)[kBank3Frags],
-                                             const int offs, const int l, const int ch = 0) {
-  bank_math<MOMENTS, SIX>(L, fr, fmr, bank_load(L, offs, l, ch), l);
+                                             const half8v (&fsw)[4], const int offs, const int l, const S3XvLane xv_img, const int ch = 0) {
+  bank_math<MOMENTS, SIX>(L, fr, fmr, fsw, bank_load<bank_folds(MOMENTS, SIX), MOMENTS>(L, offs, l, xv_img, ch), l);
 }
 
 // the outputs of one row of a placed pass (bank and ring in LDS): MODE 1 fc = 1, MODE 3 fc = 1 + the
@@ -627,18 +670,42 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       if (any_slow != (KIND == 2)) return;
     }
   }
-  half8v fr[kBank2Frags];                        // the fc = 1 bank's constant fragments
+  // the fc = 1 bank's constant fragments and the moment filters' (kinds 0 and 2), but for the four slice-2 fragments of the
+  // dominant pairs: those are fsw's, which holds what the current loop needs of them (bank_math)
+  half8v fr[kBank2Frags];
   {
     const uint4* src = reinterpret_cast<const uint4*>(kBank2Frags32) + l;
 #pragma unroll
-    for (int f = 0; f < kBank2Frags; ++f) fr[f] = __builtin_bit_cast(half8v, src[f * kWave]);
+    for (int f = 0; f < kBank2Frags; ++f) fr[f] = f == 2 || f == 7 ? half8v{} : __builtin_bit_cast(half8v, src[f * kWave]);
   }
-  half8v fmr[kBank3Frags];                       // the moment filters' (kinds 0 and 2)
+  half8v fmr[kBank3Frags];
   if constexpr (kMom) {
     const uint4* src = reinterpret_cast<const uint4*>(kBank3Frags32) + l;
 #pragma unroll
-    for (int f = 0; f < kBank3Frags; ++f) fmr[f] = __builtin_bit_cast(half8v, src[f * kWave]);
+    for (int f = 0; f < kBank3Frags; ++f) fmr[f] = f == 2 || f == 5 ? half8v{} : __builtin_bit_cast(half8v, src[f * kWave]);
   }
+  // fsw holds {V2, V3} but for a pass of regime 3, around which it is loaded with the four slice-2 fragments and with the folded ones
+  // again: a stream meets the order-6 loop rarely (never in the benchmark's files), and all 27 fragments resident would not leave
+  // the loops the registers they are scheduled in at two waves per SIMD.
+  half8v fsw[4] = {half8v{}, half8v{}, half8v{}, half8v{}};
+  auto fsw_load = [&](bool six) {
+    // (the lane as a value of this call's own: loads of constants at an address the loops do not change are hoisted out of
+    // them, and all six fragments stay resident after all)
+    int ll = l;
+    asm volatile("" : "+v"(ll));
+    const uint4* const b2 = reinterpret_cast<const uint4*>(kBank2Frags32) + ll;
+    const uint4* const b3 = reinterpret_cast<const uint4*>(kBank3Frags32) + ll;
+    if (six) {
+      fsw[0] = __builtin_bit_cast(half8v, b2[2 * kWave]);
+      fsw[1] = __builtin_bit_cast(half8v, b2[7 * kWave]);
+      fsw[2] = __builtin_bit_cast(half8v, b3[2 * kWave]);
+      fsw[3] = __builtin_bit_cast(half8v, b3[5 * kWave]);
+    } else {
+      fsw[0] = __builtin_bit_cast(half8v, reinterpret_cast<const uint4*>(kBank2FoldFrag32)[ll]);
+      if constexpr (kMom) fsw[1] = __builtin_bit_cast(half8v, reinterpret_cast<const uint4*>(kBank3FoldFrag32)[ll]);
+    }
+  };
+  fsw_load(false);
   {
     uint4* z = reinterpret_cast<uint4*>(&L.img[0][0]);
     const uint4 zero = {0u, 0u, 0u, 0u};
@@ -844,16 +911,16 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
   };
 
   // ---- the cold path: places, converts for, banks and -- unless it is a full pass the loop can take -- finishes the pass
-  // at j0, everything in order with full waits.  Returns true with P = a full pass ready for the loop (records of the two
-  // passes behind it and the ring's next two chunks landed), false when the range is done.
+  // at j0, everything in order with full waits.  Returns the regime of P = a full pass ready for the loop (records of the two
+  // passes behind it and the ring's next two chunks landed), 0 when the range is done.
 #if PAR_S2_EXP & 128
 #define S3_COUNT(k) do { if (l == 0) atomicAdd(a.redo_count + (k), 1); } while (0)
 #else
 #define S3_COUNT(k) do { } while (0)
 #endif
-  auto start_run = [&]() -> bool {
+  auto start_run = [&]() -> int {
     for (;;) {
-      if (j0 >= nJ) return false;
+      if (j0 >= nJ) return 0;
       S3_COUNT(1);
       __builtin_amdgcn_s_waitcnt(0x0F70);
       wave_lds_fence();
@@ -953,37 +1020,54 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         mode = 0;
         continue;
       }
+      // The pass's bank and, unless it is a full pass for the loop, its outputs: one block per regime, so that the four slice-2
+      // fragments of regime 3 live in that block alone (selected stage by stage, they stayed live through the other regimes' loops)
       wave_lds_fence();
       const int offs = ws - wbase - 31;
-      if (kMom && regime == 3) bank_image3m<kMom, true>(L, fr, fmr, offs, l);
-      else if (kMom && regime == 2) bank_image3m<kMom, false>(L, fr, fmr, offs, l);
-      else bank_image3m<false>(L, fr, fmr, offs, l);
-      wave_lds_fence();
-      j0 += N.nok[0] + N.nok[1];
-      ++pk;
-      rbC = (j0 + 240) >> kRecShift;
       const bool full = N.nok[1] >= 1 && N.nok[0] + N.nok[1] >= 120;
-      if (full) {
-        P = N;
-        return true;
-      }
-      float res[2];
-      if (kMom && regime == 3) out_pass(std::integral_constant<int, kMom ? 3 : 1>{}, N, res);
-      else if (kMom && regime == 2) out_pass(std::integral_constant<int, kMom ? 2 : 1>{}, N, res);
-      else out_pass(std::integral_constant<int, 1>{}, N, res);
-      if constexpr (kTwo) {                       // the other channel through the same rows
-        float res1[2];
+      auto finish = [&](auto mode_tag) {
+        constexpr int MODE = decltype(mode_tag)::value;
+        bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, fsw, offs, l, bank_xv_img(l));
         wave_lds_fence();
-        if (regime == 3) bank_image3m<true, true>(L, fr, fmr, offs, l, 1);
-        else if (regime == 2) bank_image3m<true, false>(L, fr, fmr, offs, l, 1);
-        else bank_image3m<false>(L, fr, fmr, offs, l, 1);
-        wave_lds_fence();
-        if (regime == 3) out_pass(std::integral_constant<int, 3>{}, N, res1, 1);
-        else if (regime == 2) out_pass(std::integral_constant<int, 2>{}, N, res1, 1);
-        else out_pass(std::integral_constant<int, 1>{}, N, res1, 1);
-        store_pass2(N, res, res1);
+        j0 += N.nok[0] + N.nok[1];
+        ++pk;
+        rbC = (j0 + 240) >> kRecShift;
+        if (full) return;
+        float res[2];
+        out_pass(mode_tag, N, res);
+        if constexpr (kTwo) {                     // the other channel through the same rows
+          float res1[2];
+          wave_lds_fence();
+          bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, fsw, offs, l, bank_xv_img(l), 1);
+          wave_lds_fence();
+          out_pass(mode_tag, N, res1, 1);
+          store_pass2(N, res, res1);
+        } else {
+          store_pass(N, res);
+        }
+      };
+      // (a full pass leaves with ITS block's regime for the caller to choose the loop by: chosen from `regime` again, the order-6
+      // loop could be reached from every block, and its fragments stayed live through all of them)
+      if (kMom && regime == 3) {
+        fsw_load(true);
+        finish(std::integral_constant<int, kMom ? 3 : 1>{});
+        if (full) {
+          P = N;
+          return 3;                               // (the loop's caller puts the folded fragments back)
+        }
+        fsw_load(false);
+      } else if (kMom && regime == 2) {
+        finish(std::integral_constant<int, kMom ? 2 : 1>{});
+        if (full) {
+          P = N;
+          return 2;
+        }
       } else {
-        store_pass(N, res);
+        finish(std::integral_constant<int, 1>{});
+        if (full) {
+          P = N;
+          return 1;
+        }
       }
     }
   };
@@ -995,6 +1079,14 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
   // ---- the loop: see the head of this kernel.  Leaves with P finished and j0 at a pass start_run() has to look at.
   auto hot = [&](auto mode_tag) {
     constexpr int MODE = decltype(mode_tag)::value;
+    // the lane's image in the folded slice's signal fragment (bank_load): formed here, once per run of the loop -- the order-6 loop
+    // has no use for it and no register to carry it in.  (Its value hidden: known to be 0 or one image, the OR behind the ring's
+    // mask is compiled as an add of its own.)
+    S3XvLane xv_img = {0u, 0u};
+    if constexpr (MODE != 3) {
+      xv_img = bank_xv_img(l);
+      asm volatile("" : "+v"(xv_img.at), "+v"(xv_img.img));
+    }
     // (the cold path left the loop's state in vector registers: it is wave-uniform, and stays so through the loop)
     j0 = __builtin_amdgcn_readfirstlane(j0);
     wbase = __builtin_amdgcn_readfirstlane(wbase);
@@ -1104,7 +1196,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         // PLACE(pk) waits for the records alone; the chunk and the gathers land under it
         place_next(std::true_type{}, RR);
         // BANK(pk)'s image fragments set out as soon as ws is known ...
-        const S3Frags X = bank_load(L, wsK - 31, l);
+        const S3Frags X = bank_load<MODE != 3, MODE != 1>(L, wsK - 31, l, xv_img);
         __builtin_amdgcn_sched_barrier(0);
         // ... and OUT(P)'s arithmetic runs while they are on their way.  (Pinned: left alone the compiler sinks a row's arithmetic
         // into its store's lane mask at the END of the iteration, as in the stereo loop.)
@@ -1122,21 +1214,28 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
           __builtin_amdgcn_sched_barrier(0);
           // the matrix work and the row writes (behind OUT(P)'s gathers)
           res[1] = s3_out_math<MODE>(G[1], P.s[1], P.ep[1]);
-          bank_math<true, false>(L, fr, fmr, X, l);
+          bank_math<true, false>(L, fr, fmr, fsw, X, l);
           asm volatile("" : "+v"(res[1]));
           asm volatile("" ::"v"(G[1].Mh[3]));
 #pragma unroll
-          for (int i = 0; i < 28; ++i) {                            // (the bank's 13 + 15 MFMAs)
+          for (int i = 0; i < 24; ++i) {                            // (the bank's 11 + 13 MFMAs)
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
             __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // two VALU
           }
         } else {
 #pragma unroll
-          for (int r = 0; r < 2; ++r) res[r] = s3_out_math<MODE>(G[r], P.s[r], P.ep[r]);
+          for (int r = 0; r < 2; ++r) {
+            res[r] = s3_out_math<MODE>(G[r], P.s[r], P.ep[r]);
+            // (order 6: one row after the other -- interleaved, the rows' temporaries are the kernel's register peak)
+            if constexpr (MODE == 3) {
+              asm volatile("" : "+v"(res[r]));
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
           asm volatile("" : "+v"(res[0]), "+v"(res[1]));
           __builtin_amdgcn_sched_barrier(0);
           // the matrix work and the row writes (behind OUT(P)'s gathers)
-          bank_math<MODE != 1, MODE == 3>(L, fr, fmr, X, l);
+          bank_math<MODE != 1, MODE == 3>(L, fr, fmr, fsw, X, l);
         }
         // CONV's arithmetic and image writes (behind the fragment reads), then FETCH and the stores: five memory operations, in
         // this order.  (The loop's exit margin is scalar work since r10 -- formed in place_next, min by min -- and needs no place
@@ -1159,12 +1258,12 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
         // (pinned here: left alone the compiler sinks a row's arithmetic into the store's lane mask at the END of the iteration,
         // and the gathered rows and ring samples of both channels stay live through the banks: 33 registers in scratch)
         asm volatile("" : "+v"(res[0]), "+v"(res[1]));
-        bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, P.ws - wbase - 31, l, 1);
+        bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, fsw, P.ws - wbase - 31, l, xv_img, 1);
         out_pass(mode_tag, P, res1, 1);
         asm volatile("" : "+v"(res1[0]), "+v"(res1[1]));
         place_next(std::false_type{}, PlaceRecs{});
         const int offs = wsK - 31;
-        bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, offs, l, 0);
+        bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, fsw, offs, l, xv_img, 0);
         const unsigned long long c0 = s3_convert_ch(L, w0, l, 0, true);
         const unsigned long long c1 = s3_convert_ch(L, w0 - kPass, l, 1, false);
         cok = c0 | c1;
@@ -1176,7 +1275,7 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
 #if PAR_S3_PIN_MONO
         asm volatile("" : "+v"(res[0]), "+v"(res[1]));
 #endif
-        bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, offs, l);
+        bank_image3m<MODE != 1, MODE == 3>(L, fr, fmr, fsw, offs, l, xv_img);
         // CONV: one chunk per iteration
         cok = convert_chunk(w0);
         // FETCH + stores: records of pass pk + 2, chunk conv_next + 2, then P's outputs (five memory operations, in this order)
@@ -1208,9 +1307,11 @@ __device__ __forceinline__ void sinc_pipe_body(const S2Args& a, const int bx, S3
       if (mode != 0 && s3_convert_ch(L, w0 - kPass, l, 1, false) != 0ull) mode = 0;
   };
 
-  while (start_run()) {
-    if (kMom && regime == 3) hot(std::integral_constant<int, kMom ? 3 : 1>{});
-    else if (kMom && regime == 2) hot(std::integral_constant<int, kMom ? 2 : 1>{});
+  while (const int run = start_run()) {
+    if (kMom && run == 3) {
+      hot(std::integral_constant<int, kMom ? 3 : 1>{});
+      fsw_load(false);
+    } else if (kMom && run == 2) hot(std::integral_constant<int, kMom ? 2 : 1>{});
     else hot(std::integral_constant<int, 1>{});
     // P has been finished by the loop; the pass at j0 needs the cold path
   }

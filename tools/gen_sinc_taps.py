@@ -266,6 +266,20 @@ def render():
     out.append("};")
     out.append("#endif")
     out.append("")
+    # ---- the folded third slice (r11): one fragment per dominant pair, tables of their own (the tables above stay as they are)
+    out.append("// The dominant pairs' slice 2 folded into ONE fragment each (tools/sinc2_model.py, bank_fold_fragment / moment_fold_fragment):")
+    out.append("// [64 lanes][8 halves], K group g = lane >> 4: 0 the pair's hi slice 2 x %g, 1 its lo slice 2, 2 its hi slice 2, 3 zero." % M2.LO)
+    out.append("// (Every slice-2 fragment above is zero in lanes 16-63 -- asserted by the generator: the fold rests on it.)")
+    out.append("#ifdef PAR_WANT_BANK2")
+    for name, frag in (("kBank2FoldFrag32", M2.bank_fold_fragment()), ("kBank3FoldFrag32", M2.moment_fold_fragment())):
+        fv = frag.reshape(-1, 2)
+        wv = (fv[:, 0].astype(np.uint32) | (fv[:, 1].astype(np.uint32) << 16))
+        out.append("__device__ const unsigned int %s[%d] = {" % (name, len(wv)))
+        for i in range(0, len(wv), 12):
+            out.append("  " + ", ".join("0x%08xu" % w for w in wv[i:i + 12]) + ",")
+        out.append("};")
+    out.append("#endif")
+    out.append("")
     out += ["}  // namespace par", ""]
     return "\n".join(out)
 

@@ -172,6 +172,46 @@ def moment_fragments():
     return out.view(np.uint16)
 
 
+# ---- the folded third slice (r11).  Slice 2 of a filter pair holds only the overhang, taps n = 33 - i .. 31 of positions i >= 2:
+# K entries 64 .. 69, i.e. lanes g = 0, elements j <= i - 2; lanes 16-63 are zero.  The dominant pair's three slice-2 products
+# (hi hi into e0 / a01; lo hi and hi lo into the lo accumulator) therefore fit ONE MFMA into the lo accumulator: K group g = 0
+# carries 4096 x hi (the 2^-12 of the lo accumulator brings it back; exact, a power of two), g = 1 the lo part, g = 2 hi again,
+# and the signal fragment has the hi image under g = 0, 1 and the lo image under g = 2, all at K entries 64 .. 71.
+def fold_fragment(frags, hi_frag, lo_frag):
+    """[64][8] float16 bit patterns: the slice-2 fragments `hi_frag` and `lo_frag` of `frags` folded into one"""
+    f = frags.view(np.float16).astype(np.float64)
+    for fr in (hi_frag, lo_frag):
+        assert not f[fr, 16:].any(), fr         # the fold rests on this: slice 2 lives in K group 0
+    out = np.zeros((64, 8), dtype=np.float16)
+    for m in range(16):
+        big = f[hi_frag, m] * LO
+        assert np.all(np.abs(big) < 65504.0) and np.all(big.astype(np.float16).astype(np.float64) == big)
+        out[m] = big
+        out[16 + m] = f[lo_frag, m]
+        out[32 + m] = f[hi_frag, m]
+    return out.view(np.uint16)
+
+
+def slice2_fragments(table):
+    return [fr for fr, (_, _, ks, _) in enumerate(table) if ks == 2]
+
+
+def bank_fold_fragment():
+    """V2: the (e0 d0) pair's slice 2 (fragments 2 and 7 of bank_fragments())"""
+    fr = bank_fragments()
+    for k in slice2_fragments(FRAGS):
+        assert not fr[k, 16:].any(), k
+    return fold_fragment(fr, 2, 7)
+
+
+def moment_fold_fragment():
+    """V3: the (m0 m1) pair's slice 2 (fragments 2 and 5 of moment_fragments())"""
+    fr = moment_fragments()
+    for k in slice2_fragments(MOM_FRAGS):
+        assert not fr[k, 16:].any(), k
+    return fold_fragment(fr, 2, 5)
+
+
 def h16(x):
     """float16 as the matrix cores see it: subnormals flush to zero"""
     v = np.asarray(x, dtype=np.float64).astype(np.float16).astype(np.float64)
