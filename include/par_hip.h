@@ -811,6 +811,38 @@ int par_maxmono_stft_supported(int n_fft, int hop);
 /* Frames par_maxmono_stft_f32 transforms per channel (host only, for reporting the streaming form's redundant-frame share);
  * 0 when the size is unsupported. */
 int64_t par_maxmono_stft_transformed_frames(int64_t n, int n_fft, int hop);
+/* ---- Zero-crossing flutter analysis (experiments/zerocrossing_wow.py:17-30, util/wow_detection.py:342-358) ------------------------
+ * par_crossing_smooth_f64 and par_interp_f64 are added at ABI 109: par_version() stays 109.  Both work on the caller's stream and
+ * neither synchronises the host.
+ *
+ * par_crossing_smooth_f64: crossings (DEVICE int64[c], strictly ascending: what par_zero_crossings_f64 compacts) -> n = c - 1
+ * values per output.  With d[i] = (float)(crossings[i + 1] - crossings[i]) (the difference in int64, one rounding to float32:
+ * np.diff(crossings).astype(np.float32)) and kernel (DEVICE f64[span]; the host's scipy.signal.get_window("hann", span) / span * 2,
+ * no cosine is computed on the device):
+ *   smooth[i] = sum_{j < span} (double)P[i + span + (span - 1) / 2 - j] * kernel[j]
+ *               P = np.pad(d, span, mode="reflect"), taken in closed form: q = index - span, k = q mod 2 (n - 1) (non-negative),
+ *               k >= n -> 2 (n - 1) - k, P[index] = d[k]; numpy's reflection for every pad width, wider than the array included.
+ *               This is np.convolve(P, kernel, mode="same")[span:-span].  Products and sums are float64, every rounding separate.
+ *               Summation order (fixed, the same in every run and for every launch): four partial sums over the taps j = 0, 1, 2,
+ *               3 (mod 4), each in ascending j, the up to three tail taps j >= span - span % 4 added to partial sums 0, 1, 2 in
+ *               turn, then (s0 + s1) + (s2 + s3).  Every term is non-negative, so |smooth - exact| <= (span + 2) 2^-53 exact.
+ *   freq[i]   = (sr / 2) / smooth[i]                  float64, one division
+ *   xp[i]     = (double)crossings[i] / sr + t0        two roundings: numpy's crossings[:n] / sr + t0
+ *   raw[i]    = (float)(sr / 2) / d[i]                one float32 division: the reference's "raw" curve
+ * smooth (DEVICE f64[n]) and raw (DEVICE f32[n]) may be NULL; freq and xp are DEVICE f64[n].  span in
+ * [1, PAR_CROSSING_SMOOTH_MAX_SPAN]: the periods a workgroup needs and the weights sit in LDS.  At span 1 the one weight is 2
+ * and smooth = 2 d: the reference's own result there, kept.  Null crossings / kernel / freq / xp, c < 3, span outside that range,
+ * sr not finite or not positive: PAR_ERR_ARG before any device call, nothing written. */
+#define PAR_CROSSING_SMOOTH_MAX_SPAN 4096
+int par_crossing_smooth_f64(int device, const int64_t* crossings, int64_t c, const double* kernel, int span, double sr, double t0,
+                            double* smooth, double* freq, double* xp, float* raw, void* stream);
+/* par_interp_f64: out[k] = np.interp(x[k], xp, fp), k < nx (x, out DEVICE f64[nx]; xp non-decreasing, fp: DEVICE f64[m]), numpy's
+ * arithmetic restated operation by operation (slope = (fp[j+1] - fp[j]) / (xp[j+1] - xp[j]); slope * (x - xp[j]) + fp[j], no fused
+ * multiply-add): equal to numpy bit for bit.  fp[0] below xp[0], fp[m-1] above xp[m-1]; on equal knots fp at the last of them;
+ * NaN and inf in fp propagate as numpy's; a NaN abscissa gives NaN (with one knot fp[0], as numpy).  x in any order.  nx == 0:
+ * PAR_OK, nothing done.  m < 1, nx < 0, null pointers: PAR_ERR_ARG before any device call. */
+int par_interp_f64(int device, const double* x, int64_t nx, const double* xp, const double* fp, int64_t m, double* out,
+                   void* stream);
 #ifdef __cplusplus
 }
 #endif

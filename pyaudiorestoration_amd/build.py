@@ -21,6 +21,7 @@ PER_FILE = {"pos.hip": ["-ffp-contract=off"],
             "resample_fixed.hip": ["-ffp-contract=off"],
             "dynamics.hip": ["-ffp-contract=off"],    # numpy's overlap-add and interpolation, rounding by rounding
             "pan.hip": ["-ffp-contract=off"],         # np.interp once more (np_interp.h)
+            "crossings.hip": ["-ffp-contract=off"],   # np.interp a fourth time; the smoothing sum's products and adds rounded apart
             # SLP packing into v_pk_*_f32 buys no throughput on gfx950 and costs v_mov shuffles
             "sinc.hip": ["-fno-slp-vectorize"],
             "sinc2.hip": ["-fno-slp-vectorize"],

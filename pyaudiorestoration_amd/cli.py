@@ -22,6 +22,7 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli pan --box 12,300,14,5000 --fft 4096 --overlap 8 tape.wav --out tape.pan --apply
     python -m pyaudiorestoration_amd.cli difeq transfer.wav master.wav --out eq.txt         # Differential EQ -> eq.txt, eq_L.txt, eq_R.txt
     python -m pyaudiorestoration_amd.cli cyclic side_a.wav --rpm 33.333 --pilot 3150 --resample   # cyclic wow of a pilot tone -> side_a_res.wav
+    python -m pyaudiorestoration_amd.cli flutter tape.flac --band 3000,5000 --resample            # zero-crossing flutter of a pilot tone -> tape_res.wav
 """
 import argparse
 import json
@@ -246,6 +247,15 @@ def parser():
     k.add_argument("--json", default=None, metavar="REPORT.json", help="write the figures (a list when several files are given)")
     k.add_argument("--resample", action="store_true", help="remove the measured cycle: <stem>_res.wav through the sinc resampler")
     k.add_argument("--quality", type=int, default=50, help="sinc_quality (NT) of --resample")
+    u = sub.add_parser("flutter", help="zero-crossing flutter analysis: the pitch of a clean pilot tone from the spacing of its sign changes")
+    u.add_argument("files", nargs="+")
+    u.add_argument("--band", type=pair, default=None, help="LO,HI (Hz): band-pass around the pilot first (default: no filter)")
+    u.add_argument("--order", type=int, default=3, help="order of the band-pass")
+    u.add_argument("--hop", type=int, default=256, help="samples between the points of the regular pitch curve")
+    u.add_argument("--channel", default="L", choices=("L", "R"), help="the channel the pilot is in")
+    u.add_argument("--json", default=None, metavar="REPORT.json", help="write the figures (a list when several files are given)")
+    u.add_argument("--resample", action="store_true", help="remove the measured flutter: <stem>_res.wav through the sinc resampler")
+    u.add_argument("--quality", type=int, default=50, help="sinc_quality (NT) of --resample")
     x = sub.add_parser("maxmono", help="MaxMono dropout repair of a two-track transfer: per STFT bin the louder channel -> <stem>max.wav, "
                                        "the quieter -> <stem>min.wav")
     x.add_argument("files", nargs="+")
@@ -295,6 +305,32 @@ def _cyclic(args):
         logging.info("%s: depth of the cycle %.6g octaves = %.6g semitones peak to peak", path, rep["delta_octaves"], rep["delta_semitones"])
         if args.resample:
             resampling.run((path,), signal_data=((signal, sr),), speed_curve=cyclic_wow.speed_curve(res, sr, hop), resampling_mode="Sinc",
+                           sinc_quality=args.quality)
+            rep["resampled"] = f"{os.path.splitext(path)[0]}_res.wav"
+            logging.info("wrote %s", rep["resampled"])
+        reports.append(rep)
+    if args.json:
+        with open(args.json, "w") as out:
+            json.dump(reports[0] if len(reports) == 1 else reports, out, indent=1)
+        logging.info("wrote %s", args.json)
+    return 0
+
+
+def _flutter(args):
+    from . import cyclic_wow, io_ops, resampling, zerocrossing_wow
+    if args.band is not None and len(args.band) != 2:
+        raise SystemExit("--band takes LO,HI")
+    if args.hop < 1:
+        raise SystemExit("--hop is at least 1")
+    reports = []
+    for path in args.files:
+        signal, sr, ch = io_ops.read_file(path)
+        res = zerocrossing_wow.detect_crossings(signal, sr, cyclic_wow.channel_index(args.channel, ch), args.band, args.order, args.hop)
+        rep = dict(zerocrossing_wow.report(res), file=path, sr=sr, hop=args.hop, band=args.band)
+        logging.info("%s: %d crossings, smoothing span %d; pilot at %.9g Hz, flutter %.6g %% peak to peak, %.6g %% RMS", path,
+                     rep["crossings"], rep["span"], rep["mean_hz"], rep["peak_to_peak_percent"], rep["rms_percent"])
+        if args.resample:
+            resampling.run((path,), signal_data=((signal, sr),), speed_curve=zerocrossing_wow.speed_curve(res), resampling_mode="Sinc",
                            sinc_quality=args.quality)
             rep["resampled"] = f"{os.path.splitext(path)[0]}_res.wav"
             logging.info("wrote %s", rep["resampled"])
@@ -356,6 +392,8 @@ def main(argv=None):
         return _difeq(args)
     if args.cmd == "cyclic":                    # file after file, one GPU
         return _cyclic(args)
+    if args.cmd == "flutter":                   # file after file, one GPU
+        return _flutter(args)
     if args.cmd == "maxmono":                   # file after file, one GPU
         return _maxmono(args)
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
