@@ -37,7 +37,9 @@ __global__ __launch_bounds__(256) void k_lerp(const double* __restrict__ pos, in
   if (j >= len_out) return;
   const double p = pos[j];
   float v = 0.0f;
-  if (p != p) v = __builtin_nanf("");                 // np.interp passes a NaN abscissa through
+  // np.interp passes a NaN abscissa through -- except on a single knot, where arr_interp's own branch
+  // (x < xp[0] ? left : x > xp[0] ? right : fp[0]) sends it to fp[0]
+  if (p != p) v = len_in == 1 ? sig[0] : __builtin_nanf("");
   if (p >= 0.0 && p <= (double)(len_in - 1)) {
     long long i = (long long)p;                       // floor, p >= 0
     if (i >= (long long)len_in - 1) {
