@@ -452,6 +452,38 @@ int par_gather_windows_f64(int device, const float* sig, int64_t sig_stride, int
                            const int64_t* pad_l, const int64_t* host_geom, int64_t n_win, int64_t n_out, double* out,
                            int64_t out_pitch, void* stream);
 
+/* X2 sectioned batch: experiments/group_delay.py:30-96 correlates two WHOLE signals once per frequency band.
+ * par_find_delay_sect_scratch_bytes and par_find_delay_sect_f64 are added at ABI 109: par_version() stays 109.
+ *   par_find_delay_sect_f64  find_delay for n_win pairs of rows of one shape and any length: a DEVICE f64 [n_win][a_pitch]
+ *                       (3 <= na <= 2^25 used), b DEVICE f64 [n_win][b_pitch] (1 <= nb <= 2^25 used).  The rows are only
+ *                       read; windows are the caller's business.  delay, corr: DEVICE f64 [n_win]; status: DEVICE int32
+ *                       [n_win], with par_find_delay_batch_f64's meaning (1 = peak on lag na - 1, that row NaN; a row of zeros
+ *                       is NaN with status 0).  norms: DEVICE f64 [n_win][2] = (|a_w|, |b_w|) as the search used them, or
+ *                       NULL.  same_out: DEVICE f64 [n_win][same_pitch] or NULL; when given, row w receives the na values
+ *                       of the 'same' correlation as the transforms give them -- the very doubles the peak stage compares.
+ *                       Rows are cut into sections of S = 2^section_log2 samples (12..19; 0 means 19), P = ceil(na / S) of a
+ *                       and Q = ceil(nb / S) of b, transformed at N = 2 S points.  Section pairs with the same offset
+ *                       d = p - q share one spectrum C_d = sum A_p conj(B_q): max(P, Q) transforms of the packed sections
+ *                       and P + Q - 1 of the diagonals per row, instead of 2 P Q, and every row of a pass goes through the
+ *                       same launches.  A lag receives at most two diagonals' values, added in float64 in a fixed order.
+ *                       The search is par_find_delay_batch_f64's, by the same kernels: a row's (delay, corr, status) equals
+ *                       par_find_delay_f64's bit for bit -- both end in the same exact sums over the same norms -- and does
+ *                       not depend on section_log2, the pitches, n_win, the neighbouring rows or the scratch size, while
+ *                       twice the route's worst lag error stays below kXcRivalTol (measured on same_out in
+ *                       tests/test_xcorr_sect_gpu.py) and fewer than 64 rivals are listed.  Nothing is copied to the host and
+ *                       the call does not synchronise (a device's first call of a transform size uploads its twiddles).
+ *                       A null pointer (norms and same_out excepted), na < 3, nb < 1, n_win < 0, a pitch below its length,
+ *                       section_log2 outside {0, 12..19}: PAR_ERR_ARG before any device call.  n_win == 0: PAR_OK, nothing
+ *                       done.  A row above 2^25 samples: PAR_ERR_UNSUPPORTED.
+ *   scratch             DEVICE bytes.  par_find_delay_sect_scratch_bytes gives the size for all n_win rows in one pass, capped
+ *                       at 32768 rows and at 1 GiB of transform arrays plus the per-row tables, never less than one row's
+ *                       worth (0: the shape is unsupported).  Any size from one row's worth up is accepted (less:
+ *                       PAR_ERR_WORKSPACE); the rows go through in passes of as many as it holds. */
+size_t par_find_delay_sect_scratch_bytes(int64_t na, int64_t nb, int64_t n_win, int section_log2);
+int par_find_delay_sect_f64(int device, const double* a, int64_t a_pitch, int64_t na, const double* b, int64_t b_pitch, int64_t nb,
+                            int64_t n_win, int section_log2, int ignore_phase, void* scratch, size_t scratch_bytes, double* delay,
+                            double* corr, int32_t* status, double* norms, double* same_out, int64_t same_pitch, void* stream);
+
 /* W3: sign-change indices of a (band-passed) float64 signal, ascending -- zero_crossings(a) =
  * np.where(np.bitwise_xor(a[1:] > 0, a[:-1] > 0))[0] (util/wow_detection.py:448-450), the full-rate pass of
  * ZeroCrossingTracker.trace (:340).

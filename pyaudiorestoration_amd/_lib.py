@@ -102,6 +102,9 @@ SIGNATURES = {
     "par_find_delay_batch_scratch_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i64]),
     "par_find_delay_batch_f64": (c_int, [c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_int, c_vp,
                                          ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp]),
+    "par_find_delay_sect_scratch_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i64, c_int]),
+    "par_find_delay_sect_f64": (c_int, [c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, ctypes.c_size_t,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "par_gather_windows_f64": (c_int, [c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "par_piptrack_f32": (c_int, [c_int, c_vp, c_i64, c_int, c_i64, c_float, c_float, c_int, c_dbl, c_dbl, c_dbl, c_float, c_vp, c_vp, c_vp]),
     "par_track_corr_work_len": (c_i64, [c_i64, c_int]),

@@ -261,7 +261,43 @@ def parser():
     x.add_argument("files", nargs="+")
     x.add_argument("--fft", type=int, default=512, help="FFT size")
     x.add_argument("--overlap", type=int, default=4, help="hop = fft / overlap")
+    g = sub.add_parser("groupdelay", help="group delay by bands: lag, correlation and level difference of two transfers per log-spaced band")
+    g.add_argument("file", help="the reference transfer; without --ref its channel 0 is measured against its channel 1")
+    g.add_argument("--ref", default=None, metavar="OTHER", help="the other transfer: channel 0 of FILE against channel 0 of OTHER")
+    g.add_argument("--range", type=pair, default=None, metavar="T0,T1", help="span in seconds (default: the whole signal)")
+    g.add_argument("--bands", type=pair, default=[10, 2000, 45], metavar="LO,HI,BW", help="log-spaced band edges from LO to HI Hz, (HI - LO) / BW of them")
+    g.add_argument("--min-corr", type=float, default=0.6, help="bands at or below this correlation are dropped")
+    g.add_argument("--json", default=None, metavar="OUT.json", help="write the per-band arrays")
     return ap
+
+
+def _groupdelay(args):
+    from . import group_delay, io_ops
+    if len(args.bands) != 3 or (args.range is not None and len(args.range) != 2):
+        raise SystemExit("--bands takes LO,HI,BW and --range T0,T1")
+    t0, t1 = args.range if args.range is not None else (None, None)
+    sig, sr, ch = io_ops.read_file(args.file)
+    if args.ref is None:
+        if ch < 2:
+            raise SystemExit(f"{args.file} has one channel: give the other transfer with --ref")
+        ref, src = sig[:, 0], sig[:, 1]
+    else:
+        other, sr2, _ = io_ops.read_file(args.ref)
+        if sr2 != sr:
+            raise SystemExit(f"sample rates differ: {sr} and {sr2}")
+        ref, src = sig[:, 0], other[:, 0]
+    res = group_delay.measure(ref, src, sr, args.bands[0], args.bands[1], args.bands[2], t0, t1, args.min_corr, strict=False)
+    for k in range(len(res.kept)):
+        logging.info("band %2d  %5d .. %5d Hz  lag %+.6f samples  corr %.6f  levels %.6g / %.6g%s", k, int(res.band_lo[k]),
+                     int(res.band_hi[k]), res.lags_all[k], res.correlations_all[k], res.levels_ref[k], res.levels_src[k],
+                     "" if res.kept[k] else "  (dropped)")
+    rep = dict(group_delay.report(res), file=args.file, ref=args.ref, sr=sr)
+    logging.info("%d of %d bands kept", rep["n_kept"], rep["n_bands"])
+    if args.json:
+        with open(args.json, "w") as out:
+            json.dump(rep, out, indent=1)
+        logging.info("wrote %s", args.json)
+    return 0
 
 
 def _maxmono(args):
@@ -396,6 +432,8 @@ def main(argv=None):
         return _flutter(args)
     if args.cmd == "maxmono":                   # file after file, one GPU
         return _maxmono(args)
+    if args.cmd == "groupdelay":                # one pair of transfers, one GPU
+        return _groupdelay(args)
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()
     for f in sorted(args.files, key=lambda p: -os.path.getsize(p)):     # longest first

@@ -147,3 +147,64 @@ def find_delay_batch(a, b, ignore_phase=False, window_name=None):
         na = a_t.shape[1]
         raise IndexError(f"index {na} is out of bounds for axis 0 with size {na} (row {int(bad[0])})")
     return _dev.to_host(delays), _dev.to_host(corrs)
+
+
+MAX_ROW = 1 << 25                       # samples per row of find_delay_rows (par_find_delay_sect_f64)
+
+
+def _auto_section(na, nb):
+    """section_log2 for rows of na and nb samples: the smallest section that holds a whole row (one section pair, the
+    smallest transforms) up to the library's default 2^19.  The results do not depend on the choice."""
+    lg = 12
+    while (1 << lg) < max(na, nb) and lg < 19:
+        lg += 1
+    return lg
+
+
+def find_delay_rows_dev(a_t, b_t, ignore_phase=False, section=None, want_norms=False, want_same=False, scratch_bytes=None):
+    """find_delay for every pair of rows of two 2-D float64 device tensors (W, na) and (W, nb) of ANY length up to 2^25
+    (row stride >= row length, unit element stride), in one call and without a host wait: par_find_delay_sect_f64 cuts
+    the rows into sections of 2^section samples (12..19, 0 = 19; None: the smallest that holds a row) and correlates them
+    diagonal by diagonal.  The rows are only read.  -> (delays, corrs, status[, norms (W, 2)][, same (W, na)]) device
+    tensors; status 1 where the peak sits on the last lag (that row's delay and corr are NaN).  scratch_bytes: device
+    bytes for the passes (default: what the library asks for)."""
+    dev = _dev.device_index(a_t.device)
+    if a_t.ndim != 2 or b_t.ndim != 2 or a_t.shape[0] != b_t.shape[0]:
+        raise ValueError("find_delay_rows needs (W, na) and (W, nb)")
+    W, na = a_t.shape
+    nb = b_t.shape[1]
+    if a_t.dtype != torch.float64 or b_t.dtype != torch.float64 or (W and (a_t.stride(1) != 1 or b_t.stride(1) != 1)):
+        raise ValueError("find_delay_rows_dev needs float64 rows of unit element stride")
+    sec = _auto_section(na, nb) if section is None else int(section)
+    L = _lib.lib()
+    delays = _dev.empty(W, torch.float64, dev)
+    corrs = _dev.empty(W, torch.float64, dev)
+    status = _dev.empty(W, torch.int32, dev)
+    norms = _dev.empty((W, 2), torch.float64, dev) if want_norms else None
+    same = _dev.empty((W, na), torch.float64, dev) if want_same else None
+    out = (delays, corrs, status) + ((norms,) if want_norms else ()) + ((same,) if want_same else ())
+    if W:
+        nbytes = int(L.par_find_delay_sect_scratch_bytes(na, nb, W, sec)) if scratch_bytes is None else int(scratch_bytes)
+        scratch = _dev.empty(max(nbytes, 1), torch.uint8, dev)
+        _lib.check(L.par_find_delay_sect_f64(dev, _dev.ptr(a_t), a_t.stride(0) if W > 1 else max(a_t.stride(0), na), na,
+                                             _dev.ptr(b_t), b_t.stride(0) if W > 1 else max(b_t.stride(0), nb), nb, W, sec,
+                                             int(bool(ignore_phase)), _dev.ptr(scratch), nbytes, _dev.ptr(delays), _dev.ptr(corrs),
+                                             _dev.ptr(status), _dev.ptr(norms) if want_norms else None,
+                                             _dev.ptr(same) if want_same else None, na, _dev.stream_ptr(dev)))
+    return out
+
+
+def find_delay_rows(a, b, ignore_phase=False, section=None, want_norms=False, want_same=False, scratch_bytes=None):
+    """find_delay(a[w], b[w]) for every row w of a (W, na) and b (W, nb), numpy or float64 device tensors, rows of any
+    length up to 2^25 -> (delays, corrs[, norms][, same]) as numpy arrays.  The first row whose peak sits on the last lag
+    raises the reference's IndexError, with the row's index."""
+    if ignore_phase:
+        logging.warning("Ignoring phase")
+    dev = _dev.device_index(None)
+    a_t, b_t = (s if isinstance(s, torch.Tensor) else _dev.to_dev(np.asarray(s), torch.float64, dev) for s in (a, b))
+    out = find_delay_rows_dev(a_t, b_t, ignore_phase, section, want_norms, want_same, scratch_bytes)
+    bad = np.flatnonzero(out[2].cpu().numpy() == 1)
+    if len(bad):
+        na = a_t.shape[1]
+        raise IndexError(f"index {na} is out of bounds for axis 0 with size {na} (row {int(bad[0])})")
+    return tuple(_dev.to_host(t) for t in out[:2] + out[3:])

@@ -1552,6 +1552,89 @@ static void xc_search(Lags lags, const double* a, int64_t a_pitch, int64_t na, c
                      status);
 }
 
+// ---- X2 sectioned batch (k_xcs_*): rows longer than one transform, correlated by DIAGONALS of section pairs --------------
+// Rows are cut into sections of S samples (P of a, Q of b; transforms of N = 2 S points).  Correlation is bilinear: the
+// section pair (p, q) contributes its N-point correlation at the lag offset (p - q) S, so all pairs of one diagonal
+// d = p - q share ONE spectrum C_d = sum_{p - q = d} A_p conj(B_q) and one transform back.  M = max(P, Q) transforms of
+// z_s = a_s/|a| + i b_s/|b| and D = P + Q - 1 transforms of the C_d replace the 2 P Q of the pair-by-pair form; every row
+// of a pass goes through the same launches.  Layout of a pass: Z[w][s][N], s < M (stride M N per row) for the section
+// spectra, C[w][di][N], di = d + Q - 1 < D, for the diagonals and, after the second transform, their lags.
+// z_s of every row: section s of both sides, zero-padded to N; a side that has run out of sections contributes zeros
+__global__ __launch_bounds__(256) void k_xcs_pack(const double* __restrict__ a, int64_t a_pitch, int64_t na,
+                                                  const double* __restrict__ b, int64_t b_pitch, int64_t nb,
+                                                  const XcbRow* __restrict__ rows, float2* __restrict__ Z, int64_t S, int64_t M) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y, w = blockIdx.z, N = 2 * S;
+  if (i >= N) return;
+  const int64_t t = s * S + i;
+  float2 z = make_float2(0.0f, 0.0f);
+  if (i < S) {
+    if (t < na) z.x = (float)(a[w * a_pitch + t] / rows[w].norms[0]);
+    if (t < nb) z.y = (float)(b[w * b_pitch + t] / rows[w].norms[1]);
+  }
+  Z[(w * M + s) * N + i] = z;
+}
+// conj(C_d) at bins k and N - k (k <= N/2) of diagonal di = d + Q - 1: A_p and B_q are untangled from Z_p, Z_q at the bin and
+// its mirror like k_xcb_cross does, and the <= min(P, Q) products of the diagonal are summed in float64 in the order of p.
+// One thread serves both bins of a mirror pair: the signals are real, so C_d[N-k] is the conjugate of C_d[k].
+__global__ __launch_bounds__(256) void k_xcs_diag(const float2* __restrict__ Z, float2* __restrict__ C, int64_t N, int P, int Q) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x, w = blockIdx.z;
+  if (k > N / 2) return;
+  const int di = blockIdx.y, d = di - (Q - 1), M = P > Q ? P : Q, D = P + Q - 1;
+  const int64_t km = (N - k) & (N - 1);
+  const int p0 = d > 0 ? d : 0, p1 = d + Q - 1 < P - 1 ? d + Q - 1 : P - 1;
+  const float2* Zw = Z + w * M * N;
+  double cx = 0.0, cy = 0.0;
+  for (int p = p0; p <= p1; ++p) {
+    const float2* Zp = Zw + (int64_t)p * N;
+    const float2* Zq = Zw + (int64_t)(p - d) * N;
+    const float2 pk = Zp[k], pm = Zp[km], qk = Zq[k], qm = Zq[km];
+    // A = (Zp[k] + conj Zp[N-k]) / 2, B = (Zq[k] - conj Zq[N-k]) / (2i); at bin N-k both are the conjugates (real signals)
+    const float2 A = make_float2(0.5f * (pk.x + pm.x), 0.5f * (pk.y - pm.y));
+    const float2 B = make_float2(0.5f * (qk.y + qm.y), -0.5f * (qk.x - qm.x));
+    cx += (double)A.x * (double)B.x + (double)A.y * (double)B.y;           // A conj(B)
+    cy += (double)A.y * (double)B.x - (double)A.x * (double)B.y;
+  }
+  float2* Cd = C + (w * D + di) * N;
+  Cd[k] = make_float2((float)cx, (float)-cy);                              // the conjugate, for the forward-as-inverse transform
+  if (km != k) Cd[km] = make_float2((float)cx, (float)cy);                 // C_d[N-k] = conj C_d[k]
+}
+// Lag j of row w's 'same' span out of the D transformed diagonals: l = j + (nb-1)//2 - (nb-1) is the lag in samples and
+// full[l] = sum_d c_d[l - d S] over |l - d S| < S: at most two diagonals, d0 = floor(l / S) and d0 + 1, added in that order.
+struct XcLagsOfSect {
+  const float2* __restrict__ Y;                    // [rows][D][N], the second transform's output
+  int64_t S;
+  int P, Q;
+  __device__ auto row(int64_t w, int64_t nb) const {
+    const int D = P + Q - 1, q1 = Q - 1, ls = 63 - __builtin_clzll((unsigned long long)S);
+    const int64_t n = 2 * S, s = S, off = (nb - 1) / 2 - (nb - 1);
+    const float2* Yw = Y + w * D * n;
+    const double dN = (double)n;
+    return [=](int64_t j) {
+      const int64_t l = j + off, d0 = l >> ls, m0 = l - d0 * s;             // floor division: m0 in [0, S)
+      const int64_t i0 = d0 + q1, i1 = i0 + 1;
+      double v = 0.0;
+      if (i0 >= 0 && i0 < D) v = (double)Yw[i0 * n + m0].x / dN;
+      if (m0 > 0 && i1 >= 0 && i1 < D) v += (double)Yw[i1 * n + (m0 + s)].x / dN;      // m0 - S, modulo N
+      return v;
+    };
+  }
+};
+// same_out[w][j] = the doubles k_xcb_peak compares (grid: x over lags, y over rows)
+__global__ __launch_bounds__(256) void k_xcs_same(XcLagsOfSect src, int64_t na, int64_t nb, double* __restrict__ same_out,
+                                                  int64_t same_pitch) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x, w = blockIdx.y;
+  if (j >= na) return;
+  const auto lag = src.row(w, nb);
+  same_out[w * same_pitch + j] = lag(j);
+}
+// norms[w] = (|a_w|, |b_w|) out of the row records
+__global__ __launch_bounds__(64) void k_xcs_norms_out(const XcbRow* __restrict__ rows, int64_t count, double* __restrict__ norms) {
+  const int64_t w = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (w >= count) return;
+  norms[2 * w] = rows[w].norms[0];
+  norms[2 * w + 1] = rows[w].norms[1];
+}
+
 // out[w][i] = (double)sig[(starts[w] + i - pad_l[w]) * stride] inside the window's samples, 0.0 in its padding
 // (Spectrum.get_signal, util/spectrum.py:158-171, for a batch of windows; grid: x over samples, y over windows)
 __global__ __launch_bounds__(256) void k_gather_windows(const float* __restrict__ sig, int64_t sig_stride, int64_t n,
@@ -2888,6 +2971,87 @@ int par_find_delay_batch_f64(int device, double* a, int64_t a_pitch, int64_t na,
     if (rc != PAR_OK) return rc;
     xc_search<XcLagsOfY, 256>(XcLagsOfY{Y, N}, ac, a_pitch, na, bc, b_pitch, nb, c, ignore_phase, rows, delay + w0, corr + w0, status + w0,
                               s);
+    PAR_HIP_CHECK(hipGetLastError());
+  }
+  return PAR_OK;
+}
+
+// X2 sectioned batch: find_delay for n_win pairs of read-only rows of ANY length up to 2^25 (experiments/group_delay.py
+// correlates whole files, band by band): see include/par_hip.h.  Per row of a pass two arrays of D N complex values and
+// one XcbRow; the kernels are k_xcs_* above, the transforms big_fft_c2c, the search xc_search.
+struct XcsShape {
+  int64_t S, N;
+  int P, Q, M, D;
+};
+static bool xcs_shape(int64_t na, int64_t nb, int section_log2, XcsShape* sh) {
+  if (na < 1 || nb < 1 || na > kXcMaxLen || nb > kXcMaxLen || !(section_log2 == 0 || (section_log2 >= 12 && section_log2 <= 19)))
+    return false;
+  sh->S = (int64_t)1 << (section_log2 ? section_log2 : 19);
+  sh->N = 2 * sh->S;
+  sh->P = (int)((na + sh->S - 1) / sh->S);
+  sh->Q = (int)((nb + sh->S - 1) / sh->S);
+  sh->M = sh->P > sh->Q ? sh->P : sh->Q;
+  sh->D = sh->P + sh->Q - 1;
+  return true;
+}
+static size_t xcs_row_bytes(const XcsShape& sh) { return (size_t)(2 * sh.D * sh.N) * sizeof(float2) + sizeof(par::XcbRow); }
+size_t par_find_delay_sect_scratch_bytes(int64_t na, int64_t nb, int64_t n_win, int section_log2) {
+  XcsShape sh;
+  if (!xcs_shape(na, nb, section_log2, &sh)) return 0;
+  int64_t fit = (int64_t)(kXcbCap / ((size_t)(2 * sh.D * sh.N) * sizeof(float2)));
+  if (fit > kXcbMaxPass) fit = kXcbMaxPass;
+  if (fit < 1) fit = 1;
+  int64_t c = n_win < 1 ? 1 : n_win;
+  if (c > fit) c = fit;
+  return (size_t)c * xcs_row_bytes(sh);
+}
+int par_find_delay_sect_f64(int device, const double* a, int64_t a_pitch, int64_t na, const double* b, int64_t b_pitch, int64_t nb,
+                            int64_t n_win, int section_log2, int ignore_phase, void* scratch, size_t scratch_bytes, double* delay,
+                            double* corr, int32_t* status, double* norms, double* same_out, int64_t same_pitch, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(a && b && scratch && delay && corr && status, PAR_ERR_ARG, "par_find_delay_sect_f64: null pointer");
+  PAR_REQUIRE(na >= 3 && nb >= 1 && n_win >= 0, PAR_ERR_ARG, "par_find_delay_sect_f64: na %lld (>= 3), nb %lld (>= 1), n_win %lld (>= 0)",
+              (long long)na, (long long)nb, (long long)n_win);
+  PAR_REQUIRE(a_pitch >= na && b_pitch >= nb && (!same_out || same_pitch >= na), PAR_ERR_ARG,
+              "par_find_delay_sect_f64: pitch %lld / %lld / %lld below the row length %lld / %lld / %lld", (long long)a_pitch,
+              (long long)b_pitch, (long long)same_pitch, (long long)na, (long long)nb, (long long)na);
+  PAR_REQUIRE(section_log2 == 0 || (section_log2 >= 12 && section_log2 <= 19), PAR_ERR_ARG,
+              "par_find_delay_sect_f64: section_log2 %d outside {0, 12..19}", section_log2);
+  if (n_win == 0) return PAR_OK;
+  PAR_REQUIRE(na <= kXcMaxLen && nb <= kXcMaxLen, PAR_ERR_UNSUPPORTED, "par_find_delay_sect_f64: %lld / %lld samples (limit 2^25 per row)",
+              (long long)na, (long long)nb);
+  XcsShape sh;
+  xcs_shape(na, nb, section_log2, &sh);
+  int64_t Cp = (int64_t)(scratch_bytes / xcs_row_bytes(sh));
+  PAR_REQUIRE(Cp >= 1, PAR_ERR_WORKSPACE, "par_find_delay_sect_f64: scratch holds less than one row (%zu bytes)", xcs_row_bytes(sh));
+  if (Cp > kXcbMaxPass) Cp = kXcbMaxPass;
+  if (Cp > n_win) Cp = n_win;
+  PAR_HIP_CHECK(hipSetDevice(device));
+  hipStream_t s = as_stream(stream);
+  const int64_t N = sh.N, DN = (int64_t)sh.D * N;
+  float2* X = static_cast<float2*>(scratch);        // z_s, then the diagonals C_d
+  float2* Y = X + Cp * DN;                          // the section spectra, then the diagonals' lags
+  XcbRow* rows = reinterpret_cast<XcbRow*>(Y + Cp * DN);
+  for (int64_t w0 = 0; w0 < n_win; w0 += Cp) {
+    const int64_t c = n_win - w0 < Cp ? n_win - w0 : Cp;
+    const double* ac = a + w0 * a_pitch;
+    const double* bc = b + w0 * b_pitch;
+    hipLaunchKernelGGL(k_xcb_norms, dim3(2, (unsigned)c), dim3(1024), 0, s, ac, a_pitch, na, bc, b_pitch, nb, rows);
+    hipLaunchKernelGGL(k_xcs_pack, dim3((unsigned)ceil_div(N, 256), (unsigned)sh.M, (unsigned)c), dim3(256), 0, s, ac, a_pitch, na, bc,
+                       b_pitch, nb, (const XcbRow*)rows, X, sh.S, (int64_t)sh.M);
+    int rc = big_fft_c2c(device, X, Y, N, c * sh.M, s);                 // Y = FFT(a_s + i b_s), section by section
+    if (rc != PAR_OK) return rc;
+    hipLaunchKernelGGL(k_xcs_diag, dim3((unsigned)ceil_div(N / 2 + 1, 256), (unsigned)sh.D, (unsigned)c), dim3(256), 0, s,
+                       (const float2*)Y, X, N, sh.P, sh.Q);
+    rc = big_fft_c2c(device, X, Y, N, c * sh.D, s);                     // Y = conj(N * circular correlation), diagonal by diagonal
+    if (rc != PAR_OK) return rc;
+    const XcLagsOfSect lags{Y, sh.S, sh.P, sh.Q};
+    if (same_out)
+      hipLaunchKernelGGL(k_xcs_same, dim3((unsigned)ceil_div(na, 256), (unsigned)c), dim3(256), 0, s, lags, na, nb,
+                         same_out + w0 * same_pitch, same_pitch);
+    if (norms)
+      hipLaunchKernelGGL(k_xcs_norms_out, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, s, (const XcbRow*)rows, c, norms + 2 * w0);
+    xc_search<XcLagsOfSect, 1024>(lags, ac, a_pitch, na, bc, b_pitch, nb, c, ignore_phase, rows, delay + w0, corr + w0, status + w0, s);
     PAR_HIP_CHECK(hipGetLastError());
   }
   return PAR_OK;

@@ -37,10 +37,11 @@ def _padlen(sos):
     return int(ntaps * 3)
 
 
-def sosfiltfilt_batch_dev(sos, x_t, dev=None):
+def sosfiltfilt_batch_dev(sos, x_t, dev=None, padlen=None):
     """scipy.signal.sosfiltfilt along the last axis of a 2-D float64 device tensor (n_sig, n) -- every stage one launch over the
     whole batch (K_sosfiltfilt's batched form).  sos: one cascade (n_sections, 6) for all rows, or a sequence of n_sig cascades
-    of equal section count and padding (e.g. the bands of dropouts_gui.process_heuristic).  Each row equals sosfiltfilt_dev's."""
+    of equal section count and padding (e.g. the bands of dropouts_gui.process_heuristic).  Each row equals sosfiltfilt_dev's.
+    padlen: scipy's argument of that name (None: its default, 3 ntaps); 0 filters rows the caller has extended already."""
     dev = _dev.device_index(dev if dev is not None else x_t.device)
     if x_t.ndim != 2:
         raise ValueError("x must be 2D (n_sig, n)")
@@ -51,10 +52,14 @@ def sosfiltfilt_batch_dev(sos, x_t, dev=None):
         sos = sos[None]
     if sos.ndim != 3 or sos.shape[2] != 6 or sos.shape[0] not in (1, n_sig):
         raise ValueError(f"sos must be (n_sections, 6) or ({n_sig}, n_sections, 6), got {sos.shape}")
-    pads = {_padlen(c) for c in sos}
-    if len(pads) != 1:
-        raise ValueError("the cascades of one batch must share scipy's default padlen")
-    padlen = pads.pop()
+    if padlen is None:
+        pads = {_padlen(c) for c in sos}
+        if len(pads) != 1:
+            raise ValueError("the cascades of one batch must share scipy's default padlen")
+        padlen = pads.pop()
+    padlen = int(padlen)
+    if padlen < 0:
+        raise ValueError("padlen must be non-negative")
     if n <= padlen:
         raise ValueError("The length of the input vector x must be greater than padlen, which is %d." % padlen)
     zi = np.ascontiguousarray([scipy.signal.sosfilt_zi(c) for c in sos], dtype=np.float64)
@@ -67,20 +72,21 @@ def sosfiltfilt_batch_dev(sos, x_t, dev=None):
     return y
 
 
-def bandpass_batch_dev(data_t, lowcuts, highcuts, fs, order=5, dev=None):
+def bandpass_batch_dev(data_t, lowcuts, highcuts, fs, order=5, dev=None, padlen=None):
     """butter_bandpass_filter of every row of a (n_sig, n) float64 device tensor with its own band (scalars: one band for all).
-    Every band must have both cut-offs inside (0, Nyquist) or every band the same one side (the cascades share their shape)."""
+    Every band must have both cut-offs inside (0, Nyquist) or every band the same one side (the cascades share their shape).
+    padlen: as in sosfiltfilt_batch_dev (None: scipy's default, what the reference's filter uses)."""
     n_sig = data_t.shape[0]
     lows = np.broadcast_to(np.asarray(lowcuts, dtype=np.float64), (n_sig,)) if np.ndim(lowcuts) else [lowcuts]
     highs = np.broadcast_to(np.asarray(highcuts, dtype=np.float64), (n_sig,)) if np.ndim(highcuts) else [highcuts]
     if len(lows) == 1 and len(highs) == 1:
         sos = _design(float(lows[0]), float(highs[0]), fs, order)
-        return data_t if sos is None else sosfiltfilt_batch_dev(sos, data_t, dev)
+        return data_t if sos is None else sosfiltfilt_batch_dev(sos, data_t, dev, padlen)
     lows, highs = np.broadcast_to(lows, (n_sig,)), np.broadcast_to(highs, (n_sig,))
     designs = [_design(float(a), float(b), fs, order) for a, b in zip(lows, highs)]
     if any(d is None for d in designs):
         raise ValueError("a band of the batch has no cut-off inside (0, Nyquist)")
-    return sosfiltfilt_batch_dev(np.stack(designs), data_t, dev)
+    return sosfiltfilt_batch_dev(np.stack(designs), data_t, dev, padlen)
 
 
 def _design(lowcut, highcut, fs, order):
