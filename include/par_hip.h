@@ -875,6 +875,63 @@ int par_crossing_smooth_f64(int device, const int64_t* crossings, int64_t c, con
  * PAR_OK, nothing done.  m < 1, nx < 0, null pointers: PAR_ERR_ARG before any device call. */
 int par_interp_f64(int device, const double* x, int64_t nx, const double* xp, const double* fp, int64_t m, double* out,
                    void* stream);
+/* ---- Spectrogram image (util/spectrum.py: Spectrum.update_data, SpectrumCanvas.compute_spectra, set_clims / set_cmap) -------------
+ * par_stft_peak_image_scratch_bytes, par_stft_peak_image_f32, par_peak_image_f32 and par_image_colorize_u8 are added at ABI 109:
+ * par_version() stays 109.  All work on the caller's stream and none synchronises the host.
+ *
+ * The picture is a PEAK-HOLD reduction of the float32 magnitude spectrogram to width x height cells.  Column c is the half-open
+ * frame range cols[c] = (lo, hi) (int64[width][2]), row r the half-open bin range rows[r] = (lo, hi) (int32[height][2]); the host
+ * layer's spectrogram.geometry derives both.  `cols` / `rows` are DEVICE arrays the kernels read, `cols_host` / `rows_host` HOST
+ * copies of the same numbers from which the call validates the tables and sizes its launches before any device call (the boxes /
+ * boxes_host precedent of par_stft_pan_ratio_f32).  Column ranges lie in [0, n_frames], lo <= hi, and each is either equal to its
+ * predecessor's or starts at or behind its predecessor's end; row ranges lie in [0, bins], in any order, and may overlap, their
+ * lengths summing to at most bins + height.  width, height in [1, PAR_IMAGE_MAX_SIDE].
+ * peak (DEVICE f32) is column-major like the frame-major spectrogram: cell (c, r) at peak[c * pitch + r], pitch >= height; nothing
+ * but those cells (r < height) and scratch is written.
+ *
+ * par_stft_peak_image_f32 (fused): peak[c][r] = the maximum over frames f in [cols[c]) and bins b in [rows[r]) of the float32
+ * magnitude m_f[b] par_stft_f32 mode 1 writes for the channel view x[i * x_stride] (DEVICE f32, n samples; `window` DEVICE
+ * f32[n_fft]) -- padding, framing, the repeated reflection of a signal shorter than n_fft/2, scaling and the + 1e-7f included --
+ * with bins = n_fft*zeropad/2 + 1 and n_frames = par_stft_frames(n, n_fft, hop).  A cell with no frame or no bin is 0.0f.  No
+ * spectrogram is stored; only frames some column names are transformed, and a column equal to its predecessor is transformed
+ * once.  The maximum is taken on the magnitudes' bit patterns as unsigned integers (they are positive floats; every NaN is first
+ * made 0x7fc00000, above all of them): a NaN magnitude makes its cell NaN, as np.max does, and the result is equal bit for bit to
+ * par_peak_image_f32 on the stored spectrogram, from run to run and whatever the launch shape.  Long columns are cut into chunks of
+ * at most R = max(16, ceil(F / 16384)) frames, F the frames the distinct columns name (a column of L frames into ceil(L / R)
+ * nearly equal parts): a rule of the arguments alone.  The call zero-fills the image, a column of one chunk is stored, and the
+ * chunks of a longer column meet through a vector atomic unsigned maximum on the zero-filled cells (no partial rows, no reduce
+ * kernel; a maximum has no order).  scratch: DEVICE, 8-byte aligned, par_stft_peak_image_scratch_bytes(width) = one int64 per
+ * column and one more, needs no initialisation.  n_fft*zeropad must be a power of two in [16, 16384] and n_fft even, otherwise
+ * PAR_ERR_UNSUPPORTED (compose par_stft_big_f32 mode 1 and par_peak_image_f32).  Null pointers; n, hop, zeropad, x_stride, width or
+ * height < 1; a side above PAR_IMAGE_MAX_SIDE; pitch < height; misaligned scratch; a table that breaks the rules above:
+ * PAR_ERR_ARG.  scratch_bytes too small: PAR_ERR_WORKSPACE.  All before any device call. */
+#define PAR_IMAGE_MAX_SIDE (1 << 19)
+/* Bytes of DEVICE scratch (host arithmetic; 0 for a width outside [1, PAR_IMAGE_MAX_SIDE]) */
+size_t par_stft_peak_image_scratch_bytes(int64_t width);
+int par_stft_peak_image_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, int zeropad,
+                            const float* window, const int64_t* cols, const int64_t* cols_host, const int32_t* rows,
+                            const int32_t* rows_host, int64_t width, int64_t height, float* peak, int64_t pitch, void* scratch,
+                            size_t scratch_bytes, void* stream);
+/* par_peak_image_f32 (composed): the same cells from a STORED frame-major float32 magnitude spectrogram, a chunk at a time: mag
+ * (DEVICE f32 [n_frames_chunk][mag_pitch], mag_pitch >= bins) holds frames frame_first .. frame_first + n_frames_chunk of the
+ * n_frames the tables speak of (what par_stft_f32 and par_stft_big_f32 write in mode 1).  Every cell is MAXIMISED with the chunk's
+ * part of it, peak[c][r] = max(peak[c][r], max over the column's frames inside the chunk and the row's bins), on the same bit
+ * patterns as above: the caller zero-fills the image before the first chunk, chunks may arrive in any order and their seams may
+ * fall inside a column.  One thread owns a cell per launch: no atomics.  n_frames_chunk == 0: PAR_OK, nothing done.  Null
+ * pointers, bins < 1, mag_pitch < bins, a chunk outside [0, n_frames], sides outside [1, PAR_IMAGE_MAX_SIDE], pitch < height, a
+ * table that breaks the rules: PAR_ERR_ARG before any device call. */
+int par_peak_image_f32(int device, const float* mag, int64_t mag_pitch, int64_t bins, int64_t n_frames, int64_t frame_first,
+                       int64_t n_frames_chunk, const int64_t* cols, const int64_t* cols_host, const int32_t* rows,
+                       const int32_t* rows_host, int64_t width, int64_t height, float* peak, int64_t pitch, void* stream);
+/* par_image_colorize_u8: out (DEVICE u8, ROW-major [height][width][4], row 0 first; 4-byte aligned) = lut[idx] (lut DEVICE
+ * u8[256][4], 4-byte aligned, passed through byte for byte) with, in float64,
+ *   dB = 20 log10((double) m)   m = peak[c * pitch + r], the logarithm of par_band_mean_db_f32
+ *   t = (dB - vmin) / (vmax - vmin);  idx = (int) floor(min(max(t, 0), 1) * 255 + 0.5)
+ * m == 0 (no data) or NaN gives (0, 0, 0, 0).  Against numpy's log10 an index can differ by one only where t * 255 + 0.5 lies within
+ * 1e-12 of an integer.  Null pointers, sides outside [1, PAR_IMAGE_MAX_SIDE], pitch < height, vmin >= vmax or not finite,
+ * misaligned lut or out: PAR_ERR_ARG before any device call. */
+int par_image_colorize_u8(int device, const float* peak, int64_t width, int64_t height, int64_t pitch, double vmin, double vmax,
+                          const uint8_t* lut, uint8_t* out, void* stream);
 #ifdef __cplusplus
 }
 #endif

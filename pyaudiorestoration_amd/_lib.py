@@ -149,7 +149,14 @@ SIGNATURES = {
     "par_maxmono_stft_transformed_frames": (c_i64, [c_i64, c_int, c_int]),
     "par_crossing_smooth_f64": (c_int, [c_int, c_vp, c_i64, c_vp, c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "par_interp_f64": (c_int, [c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "par_stft_peak_image_scratch_bytes": (c_sz, [c_i64]),
+    "par_stft_peak_image_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                        c_vp, c_i64, c_vp, c_sz, c_vp]),
+    "par_peak_image_f32": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                   c_vp]),
+    "par_image_colorize_u8": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_dbl, c_dbl, c_vp, c_vp, c_vp]),
 }
+IMAGE_MAX_SIDE = 1 << 19            # PAR_IMAGE_MAX_SIDE
 CROSSING_SMOOTH_MAX_SPAN = 4096     # PAR_CROSSING_SMOOTH_MAX_SPAN
 HPSS_COMPONENTS, HPSS_MASKS, HPSS_HARMONIC, HPSS_MEDIANS = 0, 1, 2, 3      # par_hpss_f32's out_kind (PAR_HPSS_*)
 NORMALIZE_SCRATCH_BYTES = 4096      # PAR_NORMALIZE_SCRATCH_BYTES

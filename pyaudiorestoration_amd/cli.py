@@ -23,6 +23,8 @@ resample on that GPU, results are written as <stem>_res<suffix>.wav like resampl
     python -m pyaudiorestoration_amd.cli difeq transfer.wav master.wav --out eq.txt         # Differential EQ -> eq.txt, eq_L.txt, eq_R.txt
     python -m pyaudiorestoration_amd.cli cyclic side_a.wav --rpm 33.333 --pilot 3150 --resample   # cyclic wow of a pilot tone -> side_a_res.wav
     python -m pyaudiorestoration_amd.cli flutter tape.flac --band 3000,5000 --resample            # zero-crossing flutter of a pilot tone -> tape_res.wav
+    python -m pyaudiorestoration_amd.cli spectrogram tape.flac --range 60,75 --freq 20,12000     # the picture -> tape_spec.png + tape_spec.json
+    python -m pyaudiorestoration_amd.cli spectrogram tape.flac --range 60,75 --at 512,300        # (s, Hz) of a pixel of that picture
 """
 import argparse
 import json
@@ -268,7 +270,44 @@ def parser():
     g.add_argument("--bands", type=pair, default=[10, 2000, 45], metavar="LO,HI,BW", help="log-spaced band edges from LO to HI Hz, (HI - LO) / BW of them")
     g.add_argument("--min-corr", type=float, default=0.6, help="bands at or below this correlation are dropped")
     g.add_argument("--json", default=None, metavar="OUT.json", help="write the per-band arrays")
+    v = sub.add_parser("spectrogram", help="the spectrogram picture the coordinates of the other tools are read from: <stem>_spec.png + .json")
+    v.add_argument("file")
+    v.add_argument("--range", type=pair, default=None, metavar="T0,T1", help="span in seconds (default: the whole file)")
+    v.add_argument("--freq", type=pair, default=None, metavar="F0,F1", help="band in Hz (default: 0 to sr / 2)")
+    v.add_argument("--size", type=ints, default=[2048, 1024], metavar="W,H", help="pixels")
+    v.add_argument("--fft", type=int, default=4096, help="FFT size")
+    v.add_argument("--overlap", type=int, default=8, help="hop = fft / overlap")
+    v.add_argument("--scale", default="mel", choices=("mel", "linear", "log"), help="frequency axis (log needs F0 > 0)")
+    v.add_argument("--clim", type=pair, default=[-120.0, 0.0], metavar="LO,HI", help="colour limits in dB (write --clim=-90,-20: a leading minus needs the = form)")
+    v.add_argument("--cmap", default="heat", help="gray, heat, or a matplotlib name where matplotlib is installed")
+    v.add_argument("--channel", default="L", help="L, R or a channel number")
+    v.add_argument("--out", default=None, metavar="PNG", help="default: <stem>_spec.png")
+    v.add_argument("--at", type=pair, default=None, metavar="X,Y", help="print the (s, Hz) of this pixel and write nothing")
     return ap
+
+
+def _spectrogram(args):
+    from . import cyclic_wow, io_ops, spectrogram
+    for name, val in (("--range", args.range), ("--freq", args.freq), ("--size", args.size), ("--clim", args.clim), ("--at", args.at)):
+        if val is not None and len(val) != 2:
+            raise SystemExit(f"{name} takes two values")
+    t0, t1 = args.range if args.range is not None else (None, None)
+    f0, f1 = args.freq if args.freq is not None else (None, None)
+    signal, sr, ch = io_ops.read_file(args.file)
+    channel = cyclic_wow.channel_index(args.channel if args.channel in ("L", "R") else int(args.channel), ch)
+    kw = dict(width=args.size[0], height=args.size[1], fft_size=args.fft, overlap=args.overlap, t0=t0, t1=t1, f0=f0, f1=f1,
+              scale=args.scale)
+    if args.at is not None:
+        geo = spectrogram.geometry(len(signal), sr, args.fft, max(1, args.fft // args.overlap), 1, args.size[0], args.size[1], t0, t1,
+                                   f0, f1, args.scale)
+        t, f = geo.to_time_freq(args.at[0], args.at[1])
+        print(f"{t!r} {f!r}")
+        return 0
+    png, meta, geo = spectrogram.render_file(args.file, args.out, signal_data=(signal, sr), vmin=args.clim[0], vmax=args.clim[1],
+                                             cmap=args.cmap, channel=channel, **kw)
+    logging.info("wrote %s and %s: %d x %d pixels of %.6g .. %.6g s, %.6g .. %.6g Hz (%s)", png, meta, geo.width, geo.height, geo.t0,
+                 geo.t1, geo.f0, geo.f1, geo.scale)
+    return 0
 
 
 def _groupdelay(args):
@@ -434,6 +473,8 @@ def main(argv=None):
         return _maxmono(args)
     if args.cmd == "groupdelay":                # one pair of transfers, one GPU
         return _groupdelay(args)
+    if args.cmd == "spectrogram":               # one file, one GPU
+        return _spectrogram(args)
     n_gpu = torch.cuda.device_count() if args.gpus <= 0 else min(args.gpus, torch.cuda.device_count())
     jobs = queue.Queue()
     for f in sorted(args.files, key=lambda p: -os.path.getsize(p)):     # longest first

@@ -19,6 +19,7 @@
 #include "db_math.h"
 #include "np_abs.h"
 #include "pan_items.h"
+#include "image_tables.h"
 #include "track_band.h"
 #include <math.h>
 #include <map>
@@ -714,6 +715,205 @@ __global__ __launch_bounds__(256) void k_mean_db_reduce(const double* __restrict
 #pragma unroll 8
   for (int64_t r = 1; r < n_runs; ++r) s += p[r * bins];
   mean[(int64_t)c * bins + b] = s / (double)n_frames;
+}
+
+// ---- spectrogram image straight from the samples (util/spectrum.py: the whole-file STFT reduced to a screen's pixels) ------------
+// The structure of k_stft_mean with a maximum in place of the sum.  A unit is one chunk of the frames of one DISTINCT column (a
+// column equal to its predecessor is served by the predecessor's units); k_image_plan turns the column table into the units'
+// prefix offsets, one int64 per column, and a frame slot finds its unit's column by bisection.  The slot transforms the chunk's
+// frames one after the other through one LDS frame and keeps the maxima of its at most 9 bins as unsigned integers
+// (image_key: positive floats order as their bit patterns, a NaN above them all).  After the run the maxima go into the frame's
+// LDS slot indexed by bin, lane j reduces rows j, j + T, ... over their bin ranges and writes them into every column of the
+// group: plain stores for a column of one chunk, otherwise a vector atomic maximum on the bit patterns into the image, which
+// k_image_zero has filled with 0.0f -- a maximum has no order, so the image does not depend on which chunk arrives first.
+// Gather, window product, transform, untangle and the magnitude are k_stft mode 1's expressions, operation by operation.
+// Slots that share a workgroup (T < 256) all make `passes` passes through fft_core, the longest chunk's frame count; a pass
+// beyond a slot's last frame transforms zeros and adds nothing.  One slot per workgroup (T >= 256) makes its own chunk's passes.
+__global__ __launch_bounds__(1024) void k_image_plan(const int64_t* __restrict__ cols, int64_t width, int64_t chunk, int64_t n_frames,
+                                                     int64_t* __restrict__ unit_off) {
+  __shared__ int64_t part[1024];
+  const int t = threadIdx.x;
+  const int64_t per = (width + 1023) / 1024;
+  const int64_t c0 = t * per < width ? t * per : width, c1 = c0 + per < width ? c0 + per : width;
+  auto chunks = [&](int64_t c) -> int64_t {
+    const int64_t lo = cols[2 * c], hi = cols[2 * c + 1];
+    if (lo < 0 || hi > n_frames || hi <= lo) return 0;                                   // (the host copy has been validated; the device one is not trusted)
+    if (c > 0 && cols[2 * c - 2] == lo && cols[2 * c - 1] == hi) return 0;
+    return (hi - lo + chunk - 1) / chunk;
+  };
+  int64_t own = 0;
+  for (int64_t c = c0; c < c1; ++c) own += chunks(c);
+  part[t] = own;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int64_t add = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int64_t run = part[t] - own;
+  for (int64_t c = c0; c < c1; ++c) {
+    unit_off[c] = run;
+    run += chunks(c);
+  }
+  if (t == 1023) unit_off[width] = part[1023];
+}
+
+__global__ __launch_bounds__(256) void k_image_zero(float* __restrict__ peak, int64_t width, int height, int64_t pitch) {
+  const int r = blockIdx.y * 256 + threadIdx.x;
+  if (r < height) peak[(int64_t)blockIdx.x * pitch + r] = 0.0f;
+}
+
+template <int LOGH, bool UNIT>
+__global__ __launch_bounds__(FftGeom<LOGH>::Threads) void k_stft_peak_image(const float* __restrict__ x, int64_t n, int64_t x_stride_arg,
+                                                                             int n_fft, int hop, const float* __restrict__ window,
+                                                                             const float2* __restrict__ tw, const float2* __restrict__ post,
+                                                                             const int64_t* __restrict__ cols, const int32_t* __restrict__ rows,
+                                                                             const int64_t* __restrict__ unit_off, int64_t width, int height,
+                                                                             float* __restrict__ peak, int64_t pitch, int64_t n_frames,
+                                                                             int64_t chunk, int64_t passes_all, int64_t n_units, float scale) {
+  const int64_t x_stride = UNIT ? 1 : x_stride_arg;
+  using G = FftGeom<LOGH>;
+  constexpr int H = G::H, T = G::T;
+  extern __shared__ __attribute__((aligned(16))) float2 lds[];
+  const int f = threadIdx.x / T, j0 = threadIdx.x - f * T;
+  float2* X = lds + f * G::FrameLds;
+  const int64_t slot = xcd_contiguous_block((n_units + G::Frames - 1) / G::Frames) * G::Frames + f;
+  // the unit's column: the last c with unit_off[c] <= slot (columns without units share their successor's offset)
+  bool owns = slot < n_units;
+  int64_t col = 0, f_first = 0, f_end = 0, n_chunks = 0, c_lo = 0, c_hi = 0;
+  if (owns) {
+    int64_t lo = 0, hi = width;
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (unit_off[mid] <= slot) lo = mid; else hi = mid;
+    }
+    col = lo;
+    c_lo = cols[2 * col];
+    c_hi = cols[2 * col + 1];
+    const int64_t k = slot - unit_off[col], len = c_hi - c_lo;
+    owns = c_lo >= 0 && c_hi <= n_frames && len > 0;
+    if (owns) {
+      n_chunks = (len + chunk - 1) / chunk;
+      owns = k >= 0 && k < n_chunks;
+    }
+    if (owns) {
+      // the column's frames in n_chunks nearly equal parts
+      f_first = c_lo + k * len / n_chunks;
+      f_end = c_lo + (k + 1) * len / n_chunks;
+    }
+  }
+  if (G::Frames == 1 && !owns) return;         // the workgroup's only slot: nobody waits for it
+  const int64_t passes = G::Frames == 1 ? f_end - f_first : passes_all;
+  constexpr int bins = H + 1, P = (H / 2) / T;
+  float2 pw[P + 1];
+#pragma unroll
+  for (int i = 0; i < P; ++i) pw[i] = post[j0 + i * T];
+  pw[P] = post[H / 2];
+  const float hs = 0.5f * scale;
+  constexpr bool kLinearPad = (T % 8) == 0;
+  constexpr int kPadStep = T + T / 8;
+  uint32_t acc[2 * P + 1] = {};
+  for (int64_t r = 0; r < passes; ++r) {
+    const int64_t fr = f_first + r;
+    const bool live = fr < f_end;
+    float2 v[8];
+    // (the opaque copy of the lane index: see k_stft_mean)
+    int j = j0;
+    if constexpr (G::Threads > 512) asm volatile("" : "+v"(j));
+    const int lp_k0 = lpad(j), lp_m0 = lpad(H - j);
+    const long long base = (long long)fr * hop - (n_fft >> 1);
+    const bool interior = live && base >= 0 && base + n_fft <= (long long)n;
+    if (interior && n_fft == 2 * H) {
+      const float* xs = x + base * x_stride;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        const float2 w = *reinterpret_cast<const float2*>(window + t0);
+        v[q] = make_float2(w.x * xs[(int64_t)t0 * x_stride], w.y * xs[(int64_t)(t0 + 1) * x_stride]);
+      }
+    } else if (interior) {
+      const float* xs = x + base * x_stride;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        float2 z = make_float2(0.0f, 0.0f);
+        if (t0 + 1 < n_fft) {
+          const float2 w = *reinterpret_cast<const float2*>(window + t0);
+          z.x = w.x * xs[(int64_t)t0 * x_stride];
+          z.y = w.y * xs[(int64_t)(t0 + 1) * x_stride];
+        } else if (t0 < n_fft) {
+          z.x = window[t0] * xs[(int64_t)t0 * x_stride];
+        }
+        v[q] = z;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int t0 = 2 * (j + q * T);
+        float2 z = make_float2(0.0f, 0.0f);
+        if (live) {
+          if (t0 < n_fft) z.x = window[t0] * x[reflect_index(base + t0, n) * x_stride];
+          if (t0 + 1 < n_fft) z.y = window[t0 + 1] * x[reflect_index(base + t0 + 1, n) * x_stride];
+        }
+        v[q] = z;
+      }
+    }
+    // fft_core synchronises the frame's lanes before its first store to X: the previous frame's untangle reads are done by then
+    fft_core<LOGH>(v, X, j, tw);
+    if (live) {
+      float mg[2 * P + 1];
+      auto keep = [&](int s, float re, float im) { mg[s] = fmaf(__builtin_amdgcn_sqrtf(fmaf(re, re, im * im)), hs, 1e-7f); };
+#pragma unroll
+      for (int i = 0; i <= P; ++i) {
+        const int k = (i < P) ? j + i * T : H / 2;
+        if (i == P && j != 0) break;
+        int sk = lpad(k), sm = lpad((H - k) & (H - 1));
+        if (kLinearPad && i < P) {
+          sk = lp_k0 + i * kPadStep;
+          sm = (i == 0 && j == 0) ? 0 : lp_m0 - i * kPadStep;
+        }
+        const float2 zk = X[sk];
+        const float2 zc = cconj(X[sm]);
+        const float2 ev = cadd(zk, zc);
+        const float2 t = cmul(pw[i], csub(zk, zc));
+        keep(2 * i, ev.x + t.y, ev.y - t.x);                     // bin k
+        if (i < P) keep(2 * i + 1, ev.x - t.y, -ev.y - t.x);     // bin H - k
+      }
+#pragma unroll
+      for (int s = 0; s <= 2 * P; ++s) {
+        if (s == 2 * P && j != 0) break;
+        const uint32_t key = image_key(mg[s]);
+        acc[s] = key > acc[s] ? key : acc[s];
+      }
+    }
+  }
+  frame_sync<T>();                                             // the last untangle reads of X are done: the slot becomes the bins' maxima
+  uint32_t* D = reinterpret_cast<uint32_t*>(X);                // D[k], k <= H: 2 FrameLds words are there
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    D[j0 + i * T] = acc[2 * i];
+    D[H - (j0 + i * T)] = acc[2 * i + 1];
+  }
+  if (j0 == 0) D[H / 2] = acc[2 * P];
+  frame_sync<T>();
+  if (!owns) return;
+  // the columns of the group: col and its successors with the same range
+  int64_t g_end = col + 1;
+  while (g_end < width && cols[2 * g_end] == c_lo && cols[2 * g_end + 1] == c_hi) ++g_end;
+  for (int r = j0; r < height; r += T) {
+    int rl = rows[2 * r], rh = rows[2 * r + 1];
+    rl = rl < 0 ? 0 : rl;
+    rh = rh > bins ? bins : rh;
+    uint32_t m = 0;
+    for (int b = rl; b < rh; ++b) m = D[b] > m ? D[b] : m;
+    if (n_chunks == 1) {
+      for (int64_t c = col; c < g_end; ++c) peak[c * pitch + r] = __uint_as_float(m);
+    } else if (m != 0) {
+      for (int64_t c = col; c < g_end; ++c)
+        __hip_atomic_fetch_max(reinterpret_cast<uint32_t*>(peak + c * pitch + r), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 // ---- Peak / Peak Track straight from the samples (util/wow_detection.py:294-327 on the frames of util/fourier.py:37-75) --------
@@ -2620,6 +2820,55 @@ int par_stft_mean_db_f32(int device, const float* x, int64_t n, int64_t x_stride
   hipLaunchKernelGGL(k_mean_db_reduce, dim3((unsigned)ceil_div(bins, 256), (unsigned)n_ch), dim3(256), 0, s, part, n_runs, bins, n_frames, mean);
   PAR_HIP_CHECK(hipGetLastError());
   return PAR_OK;
+}
+
+// Spectrogram image straight from the samples (k_image_plan + k_image_zero + k_stft_peak_image): what par_peak_image_f32 takes
+// from the mode-1 spectrogram of x, without the spectrogram.
+size_t par_stft_peak_image_scratch_bytes(int64_t width) {
+  if (width < 1 || width > par::kImageMaxSide) return 0;
+  return (size_t)(width + 1) * sizeof(int64_t);
+}
+
+int par_stft_peak_image_f32(int device, const float* x, int64_t n, int64_t x_stride, int n_fft, int hop, int zeropad,
+                            const float* window, const int64_t* cols, const int64_t* cols_host, const int32_t* rows,
+                            const int32_t* rows_host, int64_t width, int64_t height, float* peak, int64_t pitch, void* scratch,
+                            size_t scratch_bytes, void* stream) {
+  using namespace par;
+  PAR_REQUIRE(x && window && cols && cols_host && rows && rows_host && peak && scratch, PAR_ERR_ARG, "par_stft_peak_image_f32: null pointer");
+  PAR_REQUIRE(n >= 1 && x_stride >= 1 && hop >= 1 && zeropad >= 1 && n_fft >= 2 && width >= 1 && height >= 1 && width <= kImageMaxSide &&
+                  height <= kImageMaxSide && pitch >= height,
+              PAR_ERR_ARG, "par_stft_peak_image_f32: bad sizes (n %lld, stride %lld, n_fft %d, hop %d, zeropad %d, image %lld x %lld, pitch %lld)",
+              (long long)n, (long long)x_stride, n_fft, hop, zeropad, (long long)width, (long long)height, (long long)pitch);
+  PAR_REQUIRE(((uintptr_t)scratch & 7) == 0, PAR_ERR_ARG, "par_stft_peak_image_f32: scratch is not 8-byte aligned");
+  int rc = require_stft_size("par_stft_peak_image_f32", n_fft, zeropad);
+  if (rc != PAR_OK) return rc;
+  const int M = n_fft * zeropad, H = M / 2;
+  const int64_t n_frames = par_stft_frames(n, n_fft, hop);
+  ImagePlan plan;
+  rc = image_check_tables("par_stft_peak_image_f32", cols_host, rows_host, width, height, n_frames, H + 1, &plan);
+  if (rc != PAR_OK) return rc;
+  const size_t need = par_stft_peak_image_scratch_bytes(width);
+  PAR_REQUIRE(scratch_bytes >= need, PAR_ERR_WORKSPACE, "par_stft_peak_image_f32: scratch %zu < %zu", scratch_bytes, need);
+  PAR_HIP_CHECK(hipSetDevice(device));
+  Twiddles tw;
+  rc = get_twiddles(device, M, &tw);
+  if (rc != PAR_OK) return rc;
+  hipStream_t s = as_stream(stream);
+  const float scale = (float)(1.0 / sqrt((double)n_fft));
+  int64_t* unit_off = reinterpret_cast<int64_t*>(scratch);
+  hipLaunchKernelGGL(k_image_zero, dim3((unsigned)width, (unsigned)ceil_div(height, 256)), dim3(256), 0, s, peak, width, (int)height, pitch);
+  PAR_HIP_CHECK(hipGetLastError());
+  if (plan.n_units == 0) return PAR_OK;
+  hipLaunchKernelGGL(k_image_plan, dim3(1), dim3(1024), 0, s, cols, width, plan.chunk, n_frames, unit_off);
+  PAR_HIP_CHECK(hipGetLastError());
+  return dispatch_logh<3, 13>(ilog2(H), [&](auto lh) {
+    return dispatch_bool(x_stride == 1, [&](auto unit) {
+      using G = FftGeom<decltype(lh)::value>;
+      return launch_with_lds(k_stft_peak_image<decltype(lh)::value, decltype(unit)::value>, dim3(G::grid(plan.n_units)), dim3(G::Threads),
+                             G::FramesLds, device, s, x, n, x_stride, n_fft, hop, window, tw.w, tw.post, cols, rows,
+                             (const int64_t*)unit_off, width, (int)height, peak, pitch, n_frames, plan.chunk, plan.passes, plan.n_units, scale);
+    });
+  });
 }
 
 // Peak / Peak Track straight from the samples (k_stft_peak): what par_track_peak_f64 traces on the mode-1 spectrogram of x
